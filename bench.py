@@ -9,16 +9,18 @@ SR forward, ImageLoss(gradient), backward through SR net and student, [RCCL all-
 buckets, the SR bucket overlapped with the student backward], clip_grad_norm_(0.25) on the SR net, one Adam over SR net +
 student -- all hand-written HIP kernels behind libtpgsr_hip.so.  `--gpus N` runs the same step data-parallel (= C4).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--full] [--dump-outputs DIR]
     python bench.py --eval [--steps K] [--warmup W]         # throughput of the evaluation pass (one GPU), its own line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
   --config c2: TSRN without text prior (BASELINE configs[1], fp32)       --config c5: stu_iter 3, sr_share, bs 32 (configs[4])
 
-Prints ONE JSON line (rank 0).  `value` = whole-job img/s with inputs resident in HBM.  `roofline` is measured live:
-the dominant kernel family's launches (the MFMA implicit-GEMM convolution: every conv / linear forward, data-gradient and
-weight-gradient launch of the step, taken from the recorded plans of all networks) are replayed between HIP events on the stream
-they run on, shape by shape;
+Prints ONE JSON line (rank 0).  `value` = whole-job img/s with inputs resident in HBM, `ms_per_step` = wall time of one of the K timed
+steps.  A plain run measures that and nothing else; `--dump-outputs DIR` writes what the last timed step computed as .npy files.
+`--full` adds the secondary measurements below (`roofline`, `alt_precision`, `eval`, `tpg_opt`, `module_api`, `cpu_baseline`).
+`roofline` is measured live: the dominant kernel family's launches (the MFMA implicit-GEMM convolution: every conv / linear
+forward, data-gradient and weight-gradient launch of the step, taken from the recorded plans of all networks) are replayed between
+HIP events on the stream they run on, shape by shape;
 `traffic` comes from two rocprofv3 PMC passes over a few steps of the same workload (tools/pmc_step.sh; --no-traffic skips them).
 `cpu_baseline` times the CPU oracle (oracle/tpgsr_oracle.py, a port of the reference's step pinned against the imported
 reference) on this box's host cores -- rank 0, N=1 only, a bounded sample."""
@@ -310,6 +312,47 @@ def _log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_VALUES = 6 << 20      # per array: a larger one is written as a fixed seeded sample of this many of its values
+DUMP_MAX_BYTES = 64_000_000     # all arrays of one run together
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: every array as path/<name>.npy, float64 kept, anything else as float32.  An array of more than DUMP_MAX_VALUES
+    values is written as that many of its flattened values at indices drawn from a generator seeded by its name, so two runs (or two builds)
+    write the same positions."""
+    import zlib
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_MAX_VALUES:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (DUMP_MAX_VALUES,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        out[name] = t.contiguous().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    _log(f"outputs of the last timed step written to {path}: " + ", ".join(f"{n} {tuple(a.shape)}" for n, a in out.items()))
+
+
+def train_step_outputs(ts, loss):
+    """what a caller of the timed train step holds after it: the loss it returned, the last stage's SR images and text prior, the parameters
+    and gradients of the trained networks (the step's flat arena) and their BatchNorm running statistics"""
+    arrays = {"loss": loss, "sr": ts.last_sr}
+    if getattr(ts, "last_p", None) is not None:
+        arrays["prior"] = ts.last_p
+    arrays["params"], arrays["grads"] = ts.pool.flat, ts.pool.grad
+    bufs = [b.reshape(-1) for m in ts.pool.modules for b in m.buffers() if b.is_floating_point()]
+    if bufs:
+        arrays["bn_buffers"] = torch.cat(bufs)
+    return arrays
+
+
 def mfma_probe_tflops():
     """register-only v_mfma_f32_32x32x2_f32 loop: what this chip sustains at its real clock (datasheet: 157.3)"""
     from tpgsr_amd import kernels as K
@@ -386,7 +429,7 @@ def build_eval(dev, stu_iter=1):
     return ev, [sr] * stu_iter + tpgs + [rec] * 3
 
 
-def eval_bench(dev, steps, warmup, roofline=True, cpu=True):
+def eval_bench(dev, steps, warmup, roofline=True, cpu=True, dump=None):
     """`bench.py --eval`: throughput of the EVALUATION pass (the reference's only printed throughput is this loop's `fps`,
     interfaces/super_resolution.py:1373-1427).  One step = TextSREvaluator.eval_batch on a resident batch of 48: bicubic gray resize ->
     text-prior generator -> softmax prior -> SR network (eval-mode BatchNorm folded into the consumers' loaders, STN off), PSNR + SSIM of
@@ -404,6 +447,9 @@ def eval_bench(dev, steps, warmup, roofline=True, cpu=True):
         out = ev.eval_batch(lr_img, hr_img, labels)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump:
+        dump_outputs(dump, {"sr": out["images_sr"][-1], "prior": torch.stack(out["priors"]),
+                            "psnr": torch.as_tensor(out["psnr"]), "ssim": torch.as_tensor(out["ssim"])})
     # the device part alone: the SR images only (what `sr_time` brackets in the reference's loop, without its missing synchronize)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -490,11 +536,26 @@ def main():
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 PMC passes behind roofline.traffic (~1 min)")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--eval", action="store_true", help="time the EVALUATION pass instead (TextSREvaluator.eval_batch, bs 48, one GPU): its own "
-                                                        "JSON line with its own roofline; the training line carries a short `eval` key either way")
+                                                        "JSON line (with its own roofline under --full); under --full the training line carries a "
+                                                        "short `eval` key")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run the secondary measurements: convolution-family roofline + PMC traffic, `alt_precision`, the "
+                         "evaluation pass, `--tpg opt`, the `module_api` leg and the CPU baseline (the --no-* / --alt-prec options trim this set). "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, SR images, text prior, parameters, gradients, BatchNorm "
+                         "statistics; --eval: SR images, priors, PSNR, SSIM) as DIR/<name>.npy; inputs and weights are seeded, so two builds "
+                         "can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_eval_baseline() if args.config == "eval" else cpu_baseline(args.config)), file=line_out, flush=True)
         return
+    if not args.full:
+        # a plain run times the headline alone: every secondary leg below is gated on one of these
+        args.no_roofline = args.no_traffic = args.no_cpu_baseline = args.no_module_api = True
+        args.alt_prec = "none"
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -532,7 +593,7 @@ def main():
     if args.eval or args.config == "eval":
         if world > 1:
             raise SystemExit("bench.py --eval is a one-GPU measurement (the evaluation pass has no exchange step: N ranks = N replicas)")
-        res = eval_bench(dev, args.steps, args.warmup, roofline=not args.no_roofline, cpu=not args.no_cpu_baseline)
+        res = eval_bench(dev, args.steps, args.warmup, roofline=not args.no_roofline, cpu=not args.no_cpu_baseline, dump=args.dump_outputs)
         print(json.dumps(res), file=line_out, flush=True)
         return
     cfg = CONFIGS[args.config]
@@ -573,6 +634,9 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # before anything else runs: the roofline replays the step's launches on the same buffers
+        dump_outputs(args.dump_outputs, train_step_outputs(ts, loss))
 
     out = None
     if rank == 0:

@@ -27,13 +27,13 @@ for w in $WHAT; do
     tests)    timeout 900 python -m pytest tests -m gpu -q --maxfail=15 -x -p no:cacheprovider ${PYTEST_ARGS} > $OUT/tests.log 2>&1; echo "tests rc=$?" | tee -a $OUT/summary.txt; tail -5 $OUT/tests.log ;;
     tests_all) timeout 1200 python -m pytest tests -m gpu -q --maxfail=40 -p no:cacheprovider -s ${PYTEST_ARGS} > $OUT/tests.log 2>&1; echo "tests rc=$?" | tee -a $OUT/summary.txt; tail -5 $OUT/tests.log ;;
     t:*)      timeout 1500 python -m pytest $(echo ${w#t:} | tr "," " ") -m gpu -q -p no:cacheprovider ${PYTEST_ARGS} > $OUT/tests_sel.log 2>&1; echo "selected tests rc=$?" | tee -a $OUT/summary.txt; tail -8 $OUT/tests_sel.log ;;
-    bench_eval) timeout 600 python bench.py --eval --steps 60 --warmup 15 ${BENCH_ARGS} > $OUT/bench_eval.json 2> $OUT/bench_eval.err; echo "bench_eval rc=$?" | tee -a $OUT/summary.txt; summ $OUT/bench_eval.json ;;
-    bench_opt) timeout 600 python bench.py --tpg opt --steps 30 --warmup 10 --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench_opt.json 2> $OUT/bench_opt.err; echo "bench_opt rc=$?" | tee -a $OUT/summary.txt; summ $OUT/bench_opt.json ;;
-    ab_c3)    for kv in ${AB_ENV:-_=_}; do env $kv timeout 400 python bench.py --steps 40 --warmup 10 --no-traffic --no-cpu-baseline --alt-prec none ${BENCH_ARGS} > $OUT/bench_c3_$kv.json 2> $OUT/bench_c3_$kv.err; echo "== $kv"; summ $OUT/bench_c3_$kv.json | head -${AB_LINES:-6}; done ;;
+    bench_eval) timeout 600 python bench.py --full --eval --steps 60 --warmup 15 ${BENCH_ARGS} > $OUT/bench_eval.json 2> $OUT/bench_eval.err; echo "bench_eval rc=$?" | tee -a $OUT/summary.txt; summ $OUT/bench_eval.json ;;
+    bench_opt) timeout 600 python bench.py --full --tpg opt --steps 30 --warmup 10 --no-cpu-baseline ${BENCH_ARGS} > $OUT/bench_opt.json 2> $OUT/bench_opt.err; echo "bench_opt rc=$?" | tee -a $OUT/summary.txt; summ $OUT/bench_opt.json ;;
+    ab_c3)    for kv in ${AB_ENV:-_=_}; do env $kv timeout 400 python bench.py --full --steps 40 --warmup 10 --no-traffic --no-cpu-baseline --alt-prec none ${BENCH_ARGS} > $OUT/bench_c3_$kv.json 2> $OUT/bench_c3_$kv.err; echo "== $kv"; summ $OUT/bench_c3_$kv.json | head -${AB_LINES:-6}; done ;;
     plan_gaps) timeout 400 python tools/plan_gaps.py --out $OUT/plan_gaps_c3_x2.md > $OUT/plan_gaps.log 2>&1; echo "plan_gaps rc=$?" | tee -a $OUT/summary.txt; head -12 $OUT/plan_gaps_c3_x2.md ;;
-    bench_c3) timeout 600 python bench.py --steps 60 --warmup 15 ${BENCH_ARGS} > $OUT/bench_c3.json 2> $OUT/bench_c3.err; echo "bench_c3 rc=$?" | tee -a $OUT/summary.txt; summ $OUT/bench_c3.json ;;
-    bench_c2) timeout 600 python bench.py --config c2 --steps 60 --warmup 15 --no-cpu-baseline > $OUT/bench_c2.json 2> $OUT/bench_c2.err; echo "bench_c2 rc=$?" | tee -a $OUT/summary.txt; cat $OUT/bench_c2.json ;;
-    bench_c5) timeout 600 python bench.py --config c5 --steps 30 --warmup 8 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err; echo "bench_c5 rc=$?" | tee -a $OUT/summary.txt; cat $OUT/bench_c5.json ;;
+    bench_c3) timeout 600 python bench.py --full --steps 60 --warmup 15 ${BENCH_ARGS} > $OUT/bench_c3.json 2> $OUT/bench_c3.err; echo "bench_c3 rc=$?" | tee -a $OUT/summary.txt; summ $OUT/bench_c3.json ;;
+    bench_c2) timeout 600 python bench.py --full --config c2 --steps 60 --warmup 15 --no-cpu-baseline > $OUT/bench_c2.json 2> $OUT/bench_c2.err; echo "bench_c2 rc=$?" | tee -a $OUT/summary.txt; cat $OUT/bench_c2.json ;;
+    bench_c5) timeout 600 python bench.py --full --config c5 --steps 30 --warmup 8 --no-cpu-baseline > $OUT/bench_c5.json 2> $OUT/bench_c5.err; echo "bench_c5 rc=$?" | tee -a $OUT/summary.txt; cat $OUT/bench_c5.json ;;
     prof_c3)  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/prof_c3 -o c3 -- python $GRAFT_REPO_ROOT/bench.py --steps 25 --warmup 5 --no-cpu-baseline --no-roofline --alt-prec none --no-module-api > $GRAFT_REPO_ROOT/$OUT/prof_c3.log 2>&1); echo "prof_c3 rc=$?" | tee -a $OUT/summary.txt
               DB=$(find $OUT/prof_c3 -name "*.db" | head -1); [ -n "$DB" ] && python tools/rocpd_summary.py $DB $OUT/kernel_stats_c3.md > /dev/null; [ -n "$DB" ] && python tools/trace_timeline.py $DB > $OUT/timeline_c3.txt 2>&1; head -30 $OUT/kernel_stats_c3.md; find $OUT/prof_c3 -name "*.db" -size +30M -delete ;;
     prof_c2)  (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/prof_c2 -o c2 -- python $GRAFT_REPO_ROOT/bench.py --config c2 --steps 25 --warmup 5 --no-cpu-baseline --no-roofline > $GRAFT_REPO_ROOT/$OUT/prof_c2.log 2>&1); echo "prof_c2 rc=$?" | tee -a $OUT/summary.txt
