@@ -35,14 +35,29 @@ def test_ctc_psnr_ssim_kernels_vs_reference_fixture(golden_dir):
 
 @pytest.mark.parametrize("stu_iter", [1, 3])
 def test_multi_stage_inference_loop_vs_oracle(stu_iter):
+    _multi_stage_vs_oracle(stu_iter, True, False)
+
+
+@pytest.mark.parametrize("sr_share,tpg_share", [(False, False), (False, True), (True, True)])
+def test_multi_stage_inference_loop_topologies_vs_oracle(sr_share, tpg_share):
+    """stu_iter 3 with one SR net per stage (`--sr_share` off, the reference's default) and / or one shared text-prior generator"""
+    _multi_stage_vs_oracle(3, sr_share, tpg_share)
+
+
+def _multi_stage_vs_oracle(stu_iter, sr_share, tpg_share):
     from tpgsr_amd.interfaces.super_resolution import TextSREvaluator
     from tpgsr_amd.model import tsrn
     from tpgsr_amd.model.crnn import crnn
-    sd_sr = O.recipe_state_dict(O.tsrn_spec(STN=True, mask=True, text_prior=True), 41, tps_hw=(16, 64))
-    sr = tsrn.TSRN_TL(STN=True, mask=True)
-    sr.load_state_dict(sd_sr)
+    sd_srs, srs = [], []
+    for k in range(1 if sr_share else stu_iter):
+        sd = O.recipe_state_dict(O.tsrn_spec(STN=True, mask=True, text_prior=True), 41 + 10 * k, tps_hw=(16, 64))
+        m = tsrn.TSRN_TL(STN=True, mask=True)
+        m.load_state_dict(sd)
+        srs.append(m.to(DEV).eval())
+        sd_srs.append(sd)
+    sr = srs[0]
     sd_t, tpgs = [], []
-    for k in range(stu_iter):
+    for k in range(1 if tpg_share else stu_iter):
         sd = O.recipe_state_dict(O.crnn_spec(), 50 + k)
         m = crnn.CRNN(32, 1, 37, 256)
         m.load_state_dict(sd)
@@ -52,12 +67,12 @@ def test_multi_stage_inference_loop_vs_oracle(stu_iter):
     rec = crnn.CRNN(32, 1, 37, 256)
     rec.load_state_dict(sd_r)
     lr, hr = O.synthetic_batch(6, 99)
-    ev = TextSREvaluator([sr.to(DEV).eval()], tpgs, rec.to(DEV).eval(), stu_iter=stu_iter, sr_share=True, tpg_share=False)
+    ev = TextSREvaluator(srs, tpgs, rec.to(DEV).eval(), stu_iter=stu_iter, sr_share=sr_share, tpg_share=tpg_share)
     labels = ["abc", "7x", "", "hello", "q", "zz9"]
     out = ev.eval_batch(lr.to(DEV), hr.to(DEV), labels)
     torch.cuda.synchronize()
-    ref = O.tpgsr_eval_step([O.as_params(sd_sr, False)], [O.as_params(x, False) for x in sd_t], O.as_params(sd_r, False), lr, hr,
-                            stu_iter=stu_iter, sr_share=True, tpg_share=False)
+    ref = O.tpgsr_eval_step([O.as_params(x, False) for x in sd_srs], [O.as_params(x, False) for x in sd_t], O.as_params(sd_r, False), lr, hr,
+                            stu_iter=stu_iter, sr_share=sr_share, tpg_share=tpg_share)
     for i in range(stu_iter):
         e = (out["images_sr"][i].cpu() - ref["sr"][i]).abs().max().item()
         print(f"stage {i}: SR max err {e:.2e}")

@@ -217,3 +217,67 @@ def test_use_label_branch_oracle_vs_reference_fixture(golden_dir):
     r = O.tpgsr_train_step([ps], [pu], pt, opt, lr, hr, stu_iter=1, use_label=True, labels=(lv, wm, wt))
     assert abs(float(r["loss"]) - g["loss"][0]) < 1e-4 * g["loss"][0]
     assert abs(float(r["grad_norms"][0]) - g["gnorm"][0]) < 1e-3 * g["gnorm"][0]
+
+
+CASCADE_LAYOUTS = [("a", False, False), ("b", False, True), ("c", True, True)]
+
+
+def cascade_models(golden_dir, tag):
+    """(fixture, lr, hr, oracle SR param dicts, student param dicts, teacher) of tests/golden/train_cascade_topologies.npz layout `tag`:
+    the recipe seeds and the synthetic batch it was written from (tests/golden/make_golden_cascade.py)"""
+    g = _load(golden_dir, "train_cascade_topologies.npz")
+    li = [str(x) for x in g["layouts"]].index(tag)
+    sr_share, tpg_share, S = bool(g["sr_share"][li]), bool(g["tpg_share"][li]), int(g["stu_iter"])
+    sr_seed, t_seed, s_seed = (int(x) for x in g["seeds"])
+    lr, hr = O.synthetic_batch(int(g["n"]), int(g["batch_seed"]))
+    assert abs(lr.double().abs().sum().item() - float(g["checksum_lr"])) < 1e-9 * float(g["checksum_lr"])
+    assert abs(hr.double().abs().sum().item() - float(g["checksum_hr"])) < 1e-9 * float(g["checksum_hr"])
+    sd_sr = [O.recipe_state_dict(O.tsrn_spec(STN=True, mask=True, text_prior=True), sr_seed + 10 * k, tps_hw=(16, 64))
+             for k in range(1 if sr_share else S)]
+    sd_s = [O.recipe_state_dict(O.crnn_spec(), s_seed + 10 * k) for k in range(1 if tpg_share else S)]
+    return g, lr, hr, sd_sr, sd_s, O.recipe_state_dict(O.crnn_spec(), t_seed)
+
+
+@pytest.mark.parametrize("tag,sr_share,tpg_share", CASCADE_LAYOUTS)
+def test_train_cascade_topologies_vs_reference_fixture(golden_dir, tag, sr_share, tpg_share):
+    """stu_iter 3, N 4, STN on, with one SR net per stage (`--sr_share` off, the reference's default) and / or one shared text-prior
+    generator (`--tpg_share`): oracle.tpgsr_train_step against the reference's own cascade loop body (make_golden_cascade.py) -- the
+    losses, every SR net's pre-clip gradient norm, the checksums of every trained module (parameters and BatchNorm running statistics)
+    after each of two steps, every stage's step-0 arg-max prior.
+
+    The fixture was written at 8 CPU threads; the tolerances cover the oracle at any thread count (measured at 1, 2, 3, 4, 8 and 16):
+      step 0  losses 1e-5 (measured <= 8.3e-7); the LAST stage's own SR net's norm (layouts a, b) 1e-4 (<= 2.7e-5).  Every other SR net's
+              norm -- the earlier stages' nets and layout c's shared one, whose gradients reach the STN head through the TPS sampler and
+              the later stages' students -- is ill-conditioned in fp32: it moves with the CPU's reduction order by up to 9.6e-3 (fp64 does
+              not move), held at 2e-2.  Checksums 3e-5 (<= 6.8e-6: Adam's first update is ~ lr * sign(g), so the sign of a near-zero
+              gradient element moves its parameter by 2 lr).  Arg-max priors identical except at ties (at most 2 positions of 312 whose
+              top-1 / top-2 margin in the oracle's own distribution is below 1e-4; measured: at most 1).
+      step 1  after one Adam update of each arena every difference above is amplified: losses 5e-3 (<= 3.6e-3, the distill term), the
+              last stage's norm 5e-3 (<= 1.8e-3), every other norm 5e-2 (<= 2.5e-2), checksums 3e-5 (<= 1.0e-5)."""
+    g, lr, hr, sd_sr, sd_s, sd_t = cascade_models(golden_dir, tag)
+    assert (len(sd_sr) == 1) == sr_share and (len(sd_s) == 1) == tpg_share
+    ps, pu, pt = [O.as_params(x) for x in sd_sr], [O.as_params(x) for x in sd_s], O.as_params(sd_t, False)
+    opt = O.AdamState([q[k] for q in ps + pu for k in O.trainable_keys(q)])
+    checksum = lambda p: sum(v.detach().double().abs().sum().item() for v in p.values() if v.is_floating_point())
+    S = int(g["stu_iter"])
+    for step, (ltol, last_tol, gtol, ctol) in enumerate(((1e-5, 1e-4, 2e-2, 3e-5), (5e-3, 5e-3, 5e-2, 3e-5))):
+        r = O.tpgsr_train_step(ps, pu, pt, opt, lr, hr, stu_iter=S, sr_share=sr_share, tpg_share=tpg_share)
+        what = f"{tag} step{step}"
+        for key in ("loss", "loss_img", "loss_distill"):
+            _close(r[key], g[f"{tag}_{key}"][step], ltol, f"{what} {key}")
+        assert len(r["grad_norms"]) == len(ps)
+        for k, gn in enumerate(r["grad_norms"]):
+            tol = last_tol if (not sr_share and k == S - 1) else gtol
+            _close(gn, g[f"{tag}_gnorm"][step][k], tol, f"{what} gnorm[{k}]")           # (relative: the norms are >> 1)
+        for k, q in enumerate(ps):
+            ref = float(g[f"{tag}_checksum_sr"][step][k])
+            assert abs(checksum(q) - ref) <= ctol * ref, (what, "SR", k, checksum(q), ref)
+        for k, q in enumerate(pu):
+            ref = float(g[f"{tag}_checksum_stu"][step][k])
+            assert abs(checksum(q) - ref) <= ctol * ref, (what, "student", k, checksum(q), ref)
+        if step == 0:
+            pv = torch.stack(r["priors"])                                                  # (stage, T, N, C)
+            bad = torch.from_numpy(pv.argmax(-1).numpy() != g[f"{tag}_prior_argmax_step0"])
+            top2 = pv.topk(2, -1).values
+            margins = (top2[..., 0] - top2[..., 1])[bad].tolist()
+            assert int(bad.sum()) <= 2 and all(m < 1e-4 for m in margins), (what, int(bad.sum()), margins)

@@ -104,6 +104,22 @@ out["c5_bucket_order"] = order
 out["c5_bounds"] = ex.bounds
 out["c5_ranges"] = [list(ts6.pool.ranges[id(m)]) for m in ts6.pool.modules]
 out["c5_cut"] = stus6[0]._engine().early_final_offset()
+# the reference's default topology (`--sr_share` off: one SR net per stage) with three students (a) or one shared student (b), same
+# recording of the bucket launches
+for tag, tpg_share in (("a", False), ("b", True)):
+    srs7 = [tsrn.TSRN_TL(STN=True, mask=True).train() for _ in range(3)]
+    stus7 = [crnn.CRNN(32, 1, 37, 256).train() for _ in range(1 if tpg_share else 3)]
+    ts7 = TPGSRTrainStep(srs7, stus7, teacher, stu_iter=3, sr_share=False, tpg_share=tpg_share, world_size=1, force_collectives=True)
+    ts7.pool.bind(lr.device)
+    ts7._buffers(lr)
+    ex = ts7._exchanger()
+    order = []
+    ex.launch = lambda b, order=order: order.append(b)
+    ts7.step(lr, hr)
+    out[tag] = dict(order=order, bounds=ex.bounds, ranges=[list(ts7.pool.ranges[id(m)]) for m in ts7.pool.modules],
+                    sr=[ts7._buckets[("sr", id(m))] for m in srs7], final=[ts7._final_stage(m) for m in srs7 + stus7],
+                    early=[ts7._buckets.get(("early", id(m))) for m in stus7], rest=[ts7._buckets.get(("rest", id(m))) for m in stus7],
+                    n_modules=len(ts7.pool.modules))
 print("RESULT " + json.dumps(out))
 '''
 
@@ -155,6 +171,27 @@ def test_record_all_plans_without_gpu():
         assert b[2 + 2 * k] == (rng[k][1], a_k + cut)                # rest: from the end of the previous slice (alignment gap included)
     cover = sorted(b)
     assert cover[0][0] == 0 and all(cover[i][1] == cover[i + 1][0] for i in range(6)) and cover[-1][1] == rng[-1][1]
+    # `--sr_share` off: pool [SR0 | SR1 | SR2 | student(s)]; one bucket per SR net, an early / rest pair per student -- 3 + 2 * 3 buckets
+    # (a), 3 + 2 with the shared student (b).  The bounds tile [0, end of the last arena) without gap or overlap and every module's
+    # range lies inside exactly one bucket (a student's is cut at its early offset into its pair).  Each SR net is final at its own
+    # stage, so its bucket leaves there, last stage first; a shared student is final at stage 0 and has exactly ONE pair: its early
+    # bucket leaves after stage 0's SR bucket, its rest with finish().  Three students: 2, 7, 8 | 1, 5, 6 | 0, 3 (+ 4 by finish()).
+    for tag, n_stu, want_order in (("a", 3, [2, 7, 8, 1, 5, 6, 0, 3]), ("b", 1, [2, 1, 0, 3])):
+        r = res[tag]
+        b, rng = [tuple(x) for x in r["bounds"]], r["ranges"]
+        assert r["n_modules"] == 3 + n_stu and len(b) == 3 + 2 * n_stu, (tag, b)
+        cover = sorted(b)
+        assert cover[0][0] == 0 and cover[-1][1] == rng[-1][1] and all(x[1] == y[0] for x, y in zip(cover, cover[1:])), (tag, cover)
+        assert all(lo < hi for lo, hi in b), (tag, b)
+        for k, (a_k, e_k) in enumerate(rng[:3]):
+            assert [i for i, (lo, hi) in enumerate(b) if lo <= a_k and e_k <= hi] == [r["sr"][k]], (tag, k)
+        for k, (a_k, e_k) in enumerate(rng[3:]):
+            early, rest = b[r["early"][k]], b[r["rest"][k]]
+            assert early == (a_k + cut, e_k) and rest == (rng[2 + k][1], a_k + cut), (tag, k, early, rest)
+        assert r["sr"] == [0, 1, 2] and r["final"] == [0, 1, 2] + ([0, 1, 2] if n_stu == 3 else [0]), r
+        assert r["order"] == want_order, (tag, r["order"])
+        assert [o for o in r["order"] if o in r["sr"]] == [2, 1, 0]
+        assert sorted(r["order"] + [r["rest"][0]]) == list(range(len(b)))         # every bucket once; stage 0's rest by finish()
 
 
 FSCRIPT = r'''
