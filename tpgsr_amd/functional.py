@@ -250,6 +250,8 @@ class _BatchNorm(torch.autograd.Function):
         x = _c(x)
         C = x.shape[-1]
         M = x.numel() // C
+        if training and any(ctx.needs_input_grad[:3]) and not (C % 4 == 0 and C <= 1024 and 256 % (C // 4) == 0):
+            raise ValueError(f"batch_norm: the backward kernels take a channel count that is a multiple of 4 with C / 4 dividing 256, got {C}")
         dev = x.device
         scale, shift = torch.empty(C, device=dev), torch.empty(C, device=dev)
         mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
@@ -293,7 +295,9 @@ class _BatchNorm(torch.autograd.Function):
 
 
 def batch_norm(x, bn, training: bool, act: Optional[str] = None):
-    """bn: a BatchNormParams holder (weight, bias, running_mean, running_var, momentum, eps); act fused: 'relu' | 'mish' | None"""
+    """bn: a BatchNormParams holder (weight, bias, running_mean, running_var, momentum, eps); act fused: 'relu' | 'mish' | None.
+    A training-mode call that needs a gradient takes C = 4, 8, 16, ... (a multiple of 4 with C / 4 dividing 256: the vector backward
+    kernels) and raises ValueError otherwise; the backward of an eval-mode call raises RuntimeError."""
     if training and K._REC is None:      # (a recorded plan's engine counts its replays: engine_functional.py flush_counters)
         bn.num_batches_tracked += 1
     return _BatchNorm.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bool(training), bn.momentum, bn.eps, act)
@@ -385,6 +389,7 @@ class _Fork(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _chk(x)
+        ctx.set_materialize_grads(False)      # an unused consumer hands `None` to backward, not a zero tensor filled by an ATen kernel
         return x.view_as(x), x.view_as(x)
 
     @staticmethod
