@@ -150,6 +150,8 @@ extern "C" int tpgsr_gru_cell(const float* gi, const float* gh, const float* h, 
 
 // ids[n] = argmax_c logits[n][c] (first maximum, as torch.max), score[n] = softmax(logits[n])[ids[n]]; one wave per row;
 // written at ids_out[n * ld + col] / score_out[n * ld + col] so a decode loop fills its (N, max_len) result in place
+// A row without a finite maximum (all -inf, or all NaN) never satisfies `v > best`: its id stays INT_MAX and its score is NaN; the decode
+// loop's next embed_concat clamps that id to V - 1 (tests/test_metric_decode_ops_gpu.py::test_softmax_max_row_without_a_maximum).
 __global__ __launch_bounds__(64) void softmax_max_kernel(const float* __restrict__ logits, int C, int* __restrict__ ids, float* __restrict__ score,
                                                          int ld, int col, int* __restrict__ ids_next) {
   const int n = blockIdx.x, lane = threadIdx.x;

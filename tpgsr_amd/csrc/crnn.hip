@@ -1042,7 +1042,11 @@ extern "C" int tpgsr_semantic_loss_bwd(const float* p, const float* q, const flo
 //   nll      = -logsumexp(alpha_{T-1}(S-1), alpha_{T-1}(S-2))
 //   d nll / d logit[t][k] = p_t(k) - exp( logsumexp_{s: l'_s = k}(alpha_t(s) + beta_t(s)) + nll - log p_t(k) )
 // logits: element (n, t, c) at n * sn + t * st + c (the fused step keeps [N][T][C], the module API's tensor is [T][N][C]).
-// dlogits (same addressing) (+)= scale * weight[n] * d nll_n / d logits.  Infeasible targets (T too short) give nll = +inf as in ATen.
+// dlogits (same addressing) (+)= scale * weight[n] * d nll_n / d logits.  Infeasible targets (T < L + adjacent repeats) give nll = +inf as in
+// ATen; their GRADIENT stays finite here, scale * weight[n] * softmax(x) (no state has a finite alpha + beta, so the occupancy term is 0),
+// where ATen with zero_infinity=False returns NaN for the whole sample: a NaN would reach every parameter of the step through the shared
+// backward pass, and the collate (labels cut to 15, T = 26) needs 12 adjacent repeats to get here at all.  The other samples of the batch
+// are not affected.  Pinned by tests/test_loss_optim_ops_gpu.py::test_ctc_infeasible_target.
 // ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float ctc_lse2(float a, float b) {
   const float m = fmaxf(a, b);

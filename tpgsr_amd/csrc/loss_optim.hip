@@ -253,7 +253,10 @@ __global__ __launch_bounds__(256) void image_loss_bwd_kernel(const float* __rest
         float go, gt, dx, dy, t0, t1;
         gradmag(po, qh, qw, H, W, go, dx, dy);
         gradmag(pt, qh, qw, H, W, gt, t0, t1);
-        float diff = go - gt;
+        // equal central differences give equal magnitudes, sign 0 -- decided on the differences themselves: the two inlined copies of
+        // gradmag need not round alike under fma contraction (out == tgt gave +-1 ulp and a spurious L1 gradient:
+        // tests/test_loss_optim_ops_gpu.py::test_l1_terms_with_sign_zero_have_no_gradient)
+        float diff = (dx == t0 && dy == t1) ? 0.f : go - gt;
         float s = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
         float d = (which == 0) ? dx : (which == 1) ? -dx : (which == 2) ? dy : -dy;
         acc += s * d * 0.25f / go;

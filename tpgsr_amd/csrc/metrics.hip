@@ -160,7 +160,7 @@ extern "C" int tpgsr_ssim(const float* a, const float* b, const float* window, i
 // (w * . = the KS x KS window sum with zero padding) and S = A1 A2 / (B1 B2), A1 = 2 mu1 mu2 + C1, A2 = 2 (e12 - mu1 mu2) + C2,
 // B1 = mu1^2 + mu2^2 + C1, B2 = (e11 - mu1^2) + (e22 - mu2^2) + C2:
 //   pass 1 (every map pixel): G0 = dS/dmu1, G1 = dS/de11, G2 = dS/de12
-//   pass 2 (every image pixel q): dS_total/da(q) = (w * G0)(q) + 2 a(q) (w * G1)(q) + b(q) (w * G2)(q)       (the window is symmetric)
+//   pass 2 (every image pixel q): dS_total/da(q) = (w * G0)(q) + 2 a(q) (w * G1)(q) + b(q) (w * G2)(q)       (w * G = the ADJOINT of the window sum: the taps flipped, so the window need not be symmetric)
 // utils/ssim_psnr.py:30-50 (_ssim) is what autograd differentiates in the reference.
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ssim_grad_maps_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ win,
