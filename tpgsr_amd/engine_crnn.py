@@ -127,18 +127,6 @@ class LstmLayer:
             (K.lstm_seq_fwdg if gran else K.lstm_seq_fwd)(G, self.whh_f, self.bhh, Cst, out, hx, sync, N, T, Hh)
             self.emb.fwd(N, 1, T, out, e)
             return
-        if K.LSTM_STEPX and Hh == 256 and N <= 64:           # one fused launch per time step
-            if not hasattr(self, "_stepx"):
-                self._stepx = {}
-            key = K.current_stream().cuda_stream               # per stream (the teacher runs on its own)
-            if key not in self._stepx:
-                self._stepx[key] = K.lstm_stepx_buffers(self.eng.device)
-            wfr, hx = self._stepx[key]
-            K.lstm_wfrag(self.whh_f, wfr, Hh)
-            for s in range(T):
-                K.lstm_stepx_fwd(G, wfr, self.bhh, Cst, out, hx, N, T, Hh, s)
-            self.emb.fwd(N, 1, T, out, e)
-            return
         S = Hh // (32 * K.LSTM_FWD_KCHUNKS)                   # K-split of the recurrent projection: 2 * S * 4Hh/64 workgroups
         for s in range(T):
             if s > 0:     # gh = h_prev W_hh^T, both directions in one split-K launch (h_prev: time s-1 / T-s of `out`)
@@ -162,12 +150,11 @@ class LstmLayer:
         if seq:                                              # the whole BPTT recurrence as one persistent launch
             if not hasattr(self, "_seqb"):
                 self._seqb = {}
-            gran = K.LSTM_GRANULE_BWD and T <= 255
-            key = (K.current_stream().cuda_stream, gran, N)
+            key = (K.current_stream().cuda_stream, N)
             if key not in self._seqb:
-                self._seqb[key] = K.lstm_seq_bwd_granule_buffers(self.eng.device) if gran else K.lstm_seq_bwd_buffers(self.eng.device)
+                self._seqb[key] = K.lstm_seq_bwd_buffers(self.eng.device)
             px, sync = self._seqb[key]
-            (K.lstm_seq_bwdg if gran else K.lstm_seq_bwd)(G, Cst, dout, P[r + "weight_hh_l0"], P[r + "weight_hh_l0_reverse"], px, sync, N, T, Hh)
+            K.lstm_seq_bwd(G, Cst, dout, P[r + "weight_hh_l0"], P[r + "weight_hh_l0_reverse"], px, sync, N, T, Hh)
         for s in range(0 if seq else T):
             if s > 0:     # dh_prev = dG[t_next] W_hh (operand [K=4Hh][Hh] is the PyTorch weight itself), split over K
                 a = [G.data_ptr() + 4 * (((T - s if d == 0 else s - 1) * 2 + d) * G4) for d in range(2)]

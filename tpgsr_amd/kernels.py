@@ -684,23 +684,11 @@ def make_conv_args(g: ConvGeom, inp, wt=None, out=None, *, bias=None, in2=None, 
     return a
 
 
-def DRYRUN_NO_LIB() -> bool:
-    """a dry run (TPGSR_PLAN_DRYRUN=1) still loads the library for host-side queries; kept as a function so engines can ask in one place"""
-    return False
-
-
 def conv_in2_scale_ok(a: ConvArgs) -> bool:
     """will tpgsr_conv_fwd take this launch with its scaled residual operand (in2_scale)?  Only the whole-CU halo kernel's loader has it"""
     return bool(_lib.load().tpgsr_conv_in2_scale_ok(C.byref(a)))
 
 
-# TPGSR_BNB_APPLY_FOLD=1 (round 6, VERDICT round 5 item 4; OFF by default): the apply pass of a BatchNorm's backward runs on the
-# WEIGHT-GRADIENT stream only (it still produces dy for the weight gradient) and the caller's stream takes dy through the loader of the
-# consuming data-gradient convolution (tpgsr_conv_args.in2_scale, whole-CU halo kernel).  Built, tested (tests/test_conv_halo3_gpu.py,
-# the parity suite under the switch), measured on one box, interleaved: 5.456 / 5.492 ms per C3 step folded against 5.439 / 5.441 with
-# the eleven apply launches in place (profiles/r06i_bnb_apply_fold_ab.md) -- the two-operand loader has ONE register set (no load of the
-# next channel block in flight while this one is split), which costs the trunk's data gradient more than the 6-us launch it replaces.
-BNB_APPLY_FOLD = os.environ.get("TPGSR_BNB_APPLY_FOLD", "0") == "1"
 BN_COARSE_ROWS = os.environ.get("TPGSR_BN_COARSE_ROWS", "1") != "0"
 
 
@@ -1224,27 +1212,6 @@ def lstm_seq_probe_reset(device=None):
 LSTM_WGRAD_BATCH = os.environ.get("TPGSR_LSTM_WGRAD_BATCH", "1") == "1"
 
 
-# fused recurrent projection + gate step (Hh == 256, N <= 64): one 32-workgroup launch per time step instead of a 128-workgroup
-# split-K GEMM + a 96-workgroup gate kernel.  Correct, measured slower (C3 10.18 vs 10.02 ms/step): with one wave per SIMD on 32 CUs
-# every L2 round trip of the step is exposed, the two wide launches hide them -- opt-in
-LSTM_STEPX = os.environ.get("TPGSR_LSTM_STEPX", "0") == "1"
-
-
-def lstm_wfrag(whhT, wfr, Hh):
-    _launch("tpgsr_lstm_wfrag", _p(whhT), _p(wfr), Hh)
-
-
-def lstm_stepx_fwd(G, wfr, bhh, Cst, out, hx, N, T, Hh, step):
-    _launch("tpgsr_lstm_stepx_fwd", _p(G), _p(wfr), _p(bhh), _p(Cst), _p(out), _p(hx), N, T, Hh, step)
-
-
-def lstm_stepx_buffers(device):
-    """(wfr, hx): fragment planes of W_hh^T (rebuilt per pass) and the zero-initialised h exchange buffer"""
-    lib = _lib.load()
-    return (torch.empty(lib.tpgsr_lstm_wfrag_bytes(), dtype=torch.uint8, device=device),
-            torch.zeros(lib.tpgsr_lstm_seq_hx_bytes(), dtype=torch.uint8, device=device))
-
-
 def lstm_seq_fwd(G, whhT, bhh, Cst, out, hx, sync, N, T, Hh):
     _launch("tpgsr_lstm_seq_fwd", _p(G), _p(whhT), _p(bhh), _p(Cst), _p(out), _p(hx), _p(sync), N, T, Hh)
 
@@ -1257,7 +1224,6 @@ def lstm_seq_buffers(device):
 
 # data-tagged hand-off for the persistent forward kernel (8-byte {h terms, tag} granules, no arrival counter): TPGSR_LSTM_GRANULE=0 -> counter form
 LSTM_GRANULE = os.environ.get("TPGSR_LSTM_GRANULE", "1") == "1"
-LSTM_GRANULE_BWD = os.environ.get("TPGSR_LSTM_GRANULE_BWD", "0") == "1"
 
 
 def lstm_seq_fwdg(G, whhT, bhh, Cst, out, hg, sync, N, T, Hh):
