@@ -578,13 +578,6 @@ int tpgsr_lstm_rec_gemm(const float* a0, const float* a1, long long a_stride, co
  * bwd: dhc [nsplit][2][N][Hh] = W_hh^T dG of the previous backward step, dcc [N][2][Hh]. */
 int tpgsr_lstm_step_fwd(float* G, const float* gh, int nsplit, const float* bhh /* [2][4Hh], optional */, float* Cst, float* out,
                         int N, int T, int Hh, int step, void* stream);
-/* BiLSTM time step as ONE launch: recurrent projection (bf16 matrix cores, split operands, full K per workgroup) + gate math, Hh == 256,
- * N <= 64; replaces tpgsr_lstm_rec_gemm + tpgsr_lstm_step_fwd.  wfr = tpgsr_lstm_wfrag(whhT) once per pass (tpgsr_lstm_wfrag_bytes()
- * bytes); hx as for tpgsr_lstm_seq_fwd (zeroed once; step s reads parity (s-1)&1 and writes s&1). */
-long long tpgsr_lstm_wfrag_bytes(void);
-int tpgsr_lstm_wfrag(const float* whhT /* [2][Hh][4Hh] */, void* wfr, int Hh, void* stream);
-int tpgsr_lstm_stepx_fwd(float* G, const void* wfr, const float* bhh, float* Cst, float* out, void* hx, int N, int T, int Hh, int step,
-                         void* stream);
 /* BiLSTM forward as ONE persistent launch (replaces the T x (tpgsr_lstm_rec_gemm + tpgsr_lstm_step_fwd) loop; model/crnn/crnn.py:10,
  * nn.LSTM(bidirectional=True)): Hh == 256, N <= 64.  G / Cst / out as for tpgsr_lstm_step_fwd, whhT [2][Hh][4Hh] = W_hh^T of both
  * directions, bhh [2][4Hh] or NULL.  hx: exchange buffer of tpgsr_lstm_seq_hx_bytes() bytes, ZEROED ONCE by the caller (reusable across
@@ -611,11 +604,6 @@ long long tpgsr_lstm_seq_hg_bytes(void);
 int tpgsr_lstm_seq_bwd(float* G, const float* Cst, const float* dout, const float* w0, const float* w1, void* px, unsigned* sync, int N,
                        int T, int Hh, void* stream);
 long long tpgsr_lstm_seq_px_bytes(void);
-/* The backward recurrence with the data-tagged hand-off (8-byte {fp32 partial sum, tag} granules): pg of tpgsr_lstm_seq_pg_bytes() bytes and
- * sync (8 x u32) ZEROED ONCE by the caller, then owned by these launches; T <= 255. */
-int tpgsr_lstm_seq_bwdg(float* G, const float* Cst, const float* dout, const float* w0, const float* w1, void* pg, unsigned* sync, int N,
-                        int T, int Hh, void* stream);
-long long tpgsr_lstm_seq_pg_bytes(void);
 int tpgsr_lstm_step_bwd(float* G, const float* Cst, const float* dout, const float* dhc, int nsplit, float* dcc, int N, int T,
                         int Hh, int step, void* stream);
 /* p = softmax(logits [N][T][C]); prior (N,C,1,T) = p with samples [0, drop_n) zeroed (prior dropout); with q: partial

@@ -47,8 +47,9 @@ def test_binding_table_matches_header():
 def test_struct_layouts(lib):
     from tpgsr_amd import _lib
     lib.tpgsr_sizeof.restype = ctypes.c_int
-    for which, st in enumerate((_lib.ConvArgs, _lib.WgradArgs, _lib.PackDesc, _lib.WgradReduceDesc, _lib.ComposeBwdDesc)):
+    for which, st in enumerate(_lib.ABI_STRUCTS):
         assert lib.tpgsr_sizeof(which) == ctypes.sizeof(st), st.__name__
+    assert len(_lib.ABI_STRUCTS) == 11 and lib.tpgsr_sizeof(len(_lib.ABI_STRUCTS)) == -1    # the list covers every struct the library knows
 
 
 def test_error_reporting_without_gpu(lib):

@@ -180,11 +180,6 @@ _SIGS = {
     "tpgsr_lstm_seq_hg_bytes": (C.c_longlong, []),
     "tpgsr_lstm_seq_bwd": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
     "tpgsr_lstm_seq_px_bytes": (C.c_longlong, []),
-    "tpgsr_lstm_seq_bwdg": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]),
-    "tpgsr_lstm_seq_pg_bytes": (C.c_longlong, []),
-    "tpgsr_lstm_wfrag_bytes": (C.c_longlong, []),
-    "tpgsr_lstm_wfrag": (ci, [vp, vp, ci, vp]),
-    "tpgsr_lstm_stepx_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "tpgsr_lstm_step_bwd": (ci, [vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, vp]),
     "tpgsr_softmax_prior_fwd": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, ci, vp]),
     "tpgsr_semantic_loss_finalize": (ci, [vp, ci, ll, cf, vp, vp]),
@@ -252,6 +247,10 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = sorted(list(_SIGS.keys()) + ["tpgsr_last_error"])
 
+# the argument structs of the C ABI, in tpgsr_sizeof(which) order (csrc/error.cpp)
+ABI_STRUCTS = (ConvArgs, WgradArgs, PackDesc, WgradReduceDesc, ComposeBwdDesc, SplitDesc, ImageDesc, GruWgradArgs, WgradBatchItem, BnDerive,
+               BigruProjArgs)
+
 _lib = None
 
 
@@ -275,7 +274,7 @@ def load():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    for which, st in enumerate((ConvArgs, WgradArgs, PackDesc, WgradReduceDesc, ComposeBwdDesc, SplitDesc, ImageDesc, GruWgradArgs, WgradBatchItem, BnDerive, BigruProjArgs)):
+    for which, st in enumerate(ABI_STRUCTS):
         if lib.tpgsr_sizeof(which) != C.sizeof(st):
             raise TpgsrKernelError(f"ABI mismatch: {st.__name__} is {C.sizeof(st)} bytes in the binding, "
                                    f"{lib.tpgsr_sizeof(which)} in {LIB_PATH}: rebuild (python -m tpgsr_amd.build)")

@@ -597,235 +597,6 @@ __global__ __launch_bounds__(256) void lstm_seq_bwd_kernel(float* __restrict__ G
   }
 }
 
-// ------------------------------------------------------------------------------------------------------
-// backward with the DATA-TAGGED hand-off (as lstm_seq_fwdg_kernel): every partial sum travels as an 8-byte granule {fp32 value, tag =
-// (launch epoch, step)}; a consumer re-loads its 96 KB until every tag is this step's.  Twice the bytes of the counter form, but no
-// wait for the write-through acknowledgement, no arrival counter and no poll on the per-step chain.
-//   pg   [2 parity][2 dir][32 consumers][32 producers][8 units][64 rows] granules (16 MB), zeroed ONCE by the caller;
-//   sync [8] u32 as for the forward kernel (epoch in sync[4 + d]), zeroed ONCE by the caller.   T < 256.
-// ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void lstm_seq_bwdg_kernel(float* __restrict__ G, const float* __restrict__ Cst,
-                                                           const float* __restrict__ dout, const float* __restrict__ w0,
-                                                           const float* __restrict__ w1, unsigned* __restrict__ pg,
-                                                           unsigned* __restrict__ sync, int N, int T) {
-  constexpr int Hh = 256, G4 = 1024;
-  extern __shared__ __attribute__((aligned(16))) unsigned char lsb[];
-  unsigned short* wfr = reinterpret_cast<unsigned short*>(lsb);
-  float* pst = reinterpret_cast<float*>(lsb + 48 * 1024);
-  unsigned short* afr = reinterpret_cast<unsigned short*>(lsb + 48 * 1024 + 256 * LSB_PLD * 4);
-  float* rsum = reinterpret_cast<float*>(lsb + 48 * 1024 + 256 * LSB_PLD * 4 + 12 * 1024);
-  float* dcc = reinterpret_cast<float*>(lsb + 48 * 1024 + 256 * LSB_PLD * 4 + 16 * 1024);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int d = blockIdx.x / LS_NW, u = blockIdx.x % LS_NW, u0 = u * 8;
-  const float* W = d == 0 ? w0 : w1;
-  // B operand of (n-block nb, k-block kb): lane l holds unit nb 32 + (l & 31), k = 16 kb + 8 (l >> 5) + j <-> gate column (k >> 3) Hh + u0 + (k & 7)
-  for (int idx = tid; idx < 8 * 2 * 64; idx += 256) {
-    const int nb = idx >> 7, kb = (idx >> 6) & 1, l = idx & 63;
-    const int unit = nb * 32 + (l & 31);
-    unsigned short hv[8][3];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = kb * 16 + (l >> 5) * 8 + j;
-      ls_split3(W[(size_t)((k >> 3) * Hh + u0 + (k & 7)) * Hh + unit], hv[j]);
-    }
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      unsigned short* dst = wfr + ((size_t)((t * 8 + nb) * 2 + kb) * 64 + l) * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dst[j] = hv[j][t];
-    }
-  }
-  for (int i = tid; i < 3 * 2 * 2 * 64 * 8 / 2; i += 256) reinterpret_cast<unsigned*>(afr)[i] = 0u;   // rows >= N stay zero
-  for (int i = tid; i < 64 * 8; i += 256) dcc[i] = 0.f;
-  __syncthreads();
-  const int rb = wave & 1, nbh = wave >> 1;
-  const size_t dir_f = (size_t)32 * 32 * 8 * 64, par_f = 2 * dir_f;    // granules of 8 bytes {partial sum, tag}
-  const __amdgpu_buffer_rsrc_t rs_px = ls_rsrc(pg, 2 * par_f * 8);
-  const unsigned ep = sync[4 + d] & 0xffffffu;
-  const int ul = tid & 7;
-  bool tmo = false;                                  // (wave-uniform) a hand-off of this wave timed out
-  for (int s = 0; s < T; ++s) {
-    const int t = d == 0 ? T - 1 - s : s;
-    const int tp = d == 0 ? t - 1 : t + 1;           // previous state in this direction's forward order
-    const bool has_prev = d == 0 ? t > 0 : t < T - 1;
-    // everything of this step that does not depend on the exchange
-    float gt[2][4], cc[2], cp[2], dh[2];
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int n = (tid >> 3) + 32 * it;
-      if (n < N) {
-        const float* g = G + (((size_t)n * T + t) * 2 + d) * G4 + u0 + ul;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) gt[it][q] = g[q * Hh];
-        cc[it] = Cst[(((size_t)n * T + t) * 2 + d) * Hh + u0 + ul];
-        cp[it] = has_prev ? Cst[(((size_t)n * T + tp) * 2 + d) * Hh + u0 + ul] : 0.f;
-        dh[it] = dout[((size_t)n * T + t) * 2 * Hh + d * Hh + u0 + ul];
-      }
-    }
-    if (s > 0) {
-      // gather: my region [32 producers][8 units][64 rows] of granules; thread = (producer group g of 16, unit gu, row quad rq).
-      // The data is its own flag: re-load until every granule carries (epoch, step s - 1)'s tag.
-      const int g = tid >> 7, gu = (tid >> 4) & 7, rq = tid & 15;
-      float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-      const bool live = rq * 4 < N;
-      const unsigned want = (ep << 8) | (unsigned)s;
-      const unsigned base = (unsigned)((((s - 1) & 1) * par_f + d * dir_f + (size_t)u * 32 * 8 * 64) * 8);
-      ls_u32x4 v[16][2];
-      int tries = 0;
-      while (true) {
-        asm volatile("" ::: "memory");      // keeps the loads inside the retry loop (see lstm_seq_fwdg_kernel)
-        if (live) {
-#pragma unroll
-          for (int p = 0; p < 16; ++p)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh)
-              v[p][hh] = __builtin_amdgcn_raw_buffer_load_b128(
-                  rs_px, (int)(base + ((((unsigned)(g * 16 + p) * 8 + gu) * 64 + rq * 4 + hh * 2) * 8)), 0, LS_SC1);
-        }
-        unsigned bad = 0;
-        if (live) {
-#pragma unroll
-          for (int p = 0; p < 16; ++p)
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) bad |= (v[p][hh].y ^ want) | (v[p][hh].w ^ want);
-        }
-        if (__builtin_amdgcn_ballot_w64(bad != 0) == 0) break;
-        __builtin_amdgcn_s_sleep(2);
-        ++tries;
-        if (tmo || tries > LS_TRIES || ((tries & 255) == 0 && __hip_atomic_load(sync + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          if (lane == 0) __hip_atomic_store(sync + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          tmo = true;
-          break;
-        }
-      }
-      if (live) {
-#pragma unroll
-        for (int p = 0; p < 16; ++p) {     // producer order: deterministic
-          sum.x += __uint_as_float(v[p][0].x);
-          sum.y += __uint_as_float(v[p][0].z);
-          sum.z += __uint_as_float(v[p][1].x);
-          sum.w += __uint_as_float(v[p][1].z);
-        }
-      }
-      *reinterpret_cast<float4*>(rsum + ((g * 8 + gu) * 64 + rq * 4)) = sum;
-      __syncthreads();
-    }
-    // cell backward: item = (sequence n, local unit ul); the gate gradients go to G and, split, into the A fragments of the next step
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int n = (tid >> 3) + 32 * it;
-      if (n < N) {
-        const int item = n * 8 + ul;
-        const float ig = gt[it][0], fg = gt[it][1], gg = gt[it][2], og = gt[it][3];
-        float dhh = dh[it], dc = 0.f;
-        if (s > 0) {
-          dhh += rsum[ul * 64 + n] + rsum[(8 + ul) * 64 + n];
-          dc = dcc[item];
-        }
-        const float tc = gru_tanh(cc[it]);
-        const float dog = dhh * tc * og * (1.f - og);
-        dc += dhh * og * (1.f - tc * tc);
-        const float dig = dc * gg * ig * (1.f - ig);
-        const float dfg = dc * cp[it] * fg * (1.f - fg);
-        const float dgg = dc * ig * (1.f - gg * gg);
-        dcc[item] = dc * fg;
-        float* g = G + (((size_t)n * T + t) * 2 + d) * G4 + u0 + ul;
-        const float po = tmo ? __builtin_nanf("") : 0.f;
-        g[0] = tmo ? po : dig;
-        g[Hh] = tmo ? po : dfg;
-        g[2 * Hh] = tmo ? po : dgg;
-        g[3 * Hh] = tmo ? po : dog;
-        const float dq[4] = {dig, dfg, dgg, dog};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {       // k = 8 q + ul: k-block q >> 1, fragment lane (q & 1) 32 + (n & 31), element ul
-          unsigned short hv[3];
-          ls_split3(dq[q], hv);
-#pragma unroll
-          for (int tt = 0; tt < 3; ++tt)
-            afr[((size_t)((tt * 2 + (n >> 5)) * 2 + (q >> 1)) * 64 + (q & 1) * 32 + (n & 31)) * 8 + ul] = hv[tt];
-        }
-      }
-    }
-    if (s + 1 < T) {
-      __syncthreads();
-      // P_u[n][256] = dG_u[n][32] W_hh[cols_u][256]: wave (row block rb, n-blocks 4 nbh .. 4 nbh + 3)
-      ls_bf16x8 a[2][3];
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int tt = 0; tt < 3; ++tt) a[kb][tt] = *reinterpret_cast<const ls_bf16x8*>(afr + ((size_t)((tt * 2 + rb) * 2 + kb) * 64 + lane) * 8);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int nb = nbh * 4 + i;
-        floatx16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-          ls_bf16x8 b[3];
-#pragma unroll
-          for (int tt = 0; tt < 3; ++tt) b[tt] = *reinterpret_cast<const ls_bf16x8*>(wfr + ((size_t)((tt * 8 + nb) * 2 + kb) * 64 + lane) * 8);
-          acc = ls_mfma6(a[kb], b, acc);
-        }
-        // staging image [unit][row]: a lane holds 4 consecutive rows of one unit per register quad
-        const int unit = nb * 32 + (lane & 31);
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          const int row = rb * 32 + 8 * rg + 4 * (lane >> 5);
-          *reinterpret_cast<float4*>(pst + unit * LSB_PLD + row) = make_float4(acc[4 * rg], acc[4 * rg + 1], acc[4 * rg + 2], acc[4 * rg + 3]);
-        }
-      }
-      __syncthreads();
-      // publish, coalesced: piece o = (unit, row quad) = four tagged granules = two 16-byte write-through stores; nothing waits for them
-      const unsigned wbase = (unsigned)(((s & 1) * par_f + d * dir_f) * 8);
-      const unsigned tagv = (ep << 8) | (unsigned)(s + 1);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int o = tid + 256 * i, unit = o >> 4, rq = o & 15;
-        if (rq * 4 < N) {
-          const ls_u32x4 v = *reinterpret_cast<const ls_u32x4*>(pst + unit * LSB_PLD + rq * 4);
-          const unsigned off = wbase + (((((unsigned)(unit >> 3) * 32 + u) * 8 + (unit & 7)) * 64 + rq * 4) * 8);
-          ls_u32x4 lo, hi;
-          lo.x = v.x; lo.y = tagv; lo.z = v.y; lo.w = tagv;
-          hi.x = v.z; hi.y = tagv; hi.z = v.w; hi.w = tagv;
-          __builtin_amdgcn_raw_buffer_store_b128(lo, rs_px, (int)off, 0, LS_SC1);
-          __builtin_amdgcn_raw_buffer_store_b128(hi, rs_px, (int)(off + 16), 0, LS_SC1);
-        }
-      }
-    }
-  }
-  if (u == 0 && tid == 0) sync[4 + d] = ep + 1;     // see lstm_seq_fwdg_kernel
-}
-
-
-extern "C" long long tpgsr_lstm_seq_pg_bytes(void) { return 2ll * 2 * 32 * 32 * 8 * 64 * 8; }
-
-extern "C" int tpgsr_lstm_seq_bwdg(float* G, const float* Cst, const float* dout, const float* w0, const float* w1, void* pg,
-                                   unsigned* sync, int N, int T, int Hh, void* stream) {
-  TPGSR_CHECK_ARG(G && Cst && dout && w0 && w1 && pg && sync && N > 0 && N <= 64 && T > 0 && T < 256 && Hh == 256,
-                  "tpgsr_lstm_seq_bwdg: needs Hh == 256, 1 <= N <= 64, 1 <= T <= 255 and non-null buffers (got Hh %d, N %d, T %d)", Hh, N, T);
-  {   // opt in to > 64 KB of dynamic LDS, once per device
-    static std::mutex mu;
-    static unsigned long long done = 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-      tpgsr_set_error("tpgsr_lstm_seq_bwdg: hipGetDevice failed");
-      return TPGSR_ERR_LAUNCH;
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    if (!(done >> dev & 1ull)) {
-      if (hipFuncSetAttribute((const void*)lstm_seq_bwdg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LSB_LDS) != hipSuccess) {
-        tpgsr_set_error("tpgsr_lstm_seq_bwdg: LDS opt-in (%d bytes) failed", LSB_LDS);
-        return TPGSR_ERR_LAUNCH;
-      }
-      done |= 1ull << dev;
-    }
-  }
-  hipLaunchKernelGGL(lstm_seq_bwdg_kernel, dim3(2 * LS_NW), dim3(256), LSB_LDS, (hipStream_t)stream, G, Cst, dout, w0, w1, (unsigned*)pg, sync, N,
-                     T);
-  TPGSR_LAUNCH_CHECK("tpgsr_lstm_seq_bwdg");
-}
-
 extern "C" long long tpgsr_lstm_seq_px_bytes(void) { return 2ll * 2 * 32 * 32 * 8 * 64 * 4; }
 
 extern "C" int tpgsr_lstm_seq_bwd(float* G, const float* Cst, const float* dout, const float* w0, const float* w1, void* px,

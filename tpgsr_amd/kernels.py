@@ -1240,16 +1240,6 @@ def lstm_seq_bwd(G, Cst, dout, w0, w1, px, sync, N, T, Hh):
     _launch("tpgsr_lstm_seq_bwd", _p(G), _p(Cst), _p(dout), _p(w0), _p(w1), _p(px), _p(sync), N, T, Hh)
 
 
-def lstm_seq_bwdg(G, Cst, dout, w0, w1, pg, sync, N, T, Hh):
-    _launch("tpgsr_lstm_seq_bwdg", _p(G), _p(Cst), _p(dout), _p(w0), _p(w1), _p(pg), _p(sync), N, T, Hh)
-
-
-def lstm_seq_bwd_granule_buffers(device):
-    """(pg, sync) for lstm_seq_bwdg: zeroed ONCE here, then owned by the launches"""
-    return (torch.zeros(_lib.load().tpgsr_lstm_seq_pg_bytes(), dtype=torch.uint8, device=device),
-            torch.zeros(8, dtype=torch.int32, device=device))
-
-
 def lstm_seq_bwd_buffers(device):
     """(px, sync) for lstm_seq_bwd (no initialisation needed: every word read in a step was written in the step before)"""
     px = torch.empty(_lib.load().tpgsr_lstm_seq_px_bytes(), dtype=torch.uint8, device=device)
