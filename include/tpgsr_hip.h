@@ -490,6 +490,14 @@ int tpgsr_bigru_bwd(const float* gates, const float* h_out, const float* dh_out,
  * the r and z planes of dgh equal dgi's, and tpgsr_gru_wgrad reads them there. */
 int tpgsr_bigru_bwd2(const float* gates, const float* h_out, const float* dh_out, const float* dh_out2,
                      const float* w_hh, int N, int H, int W, int axis, float* dgi, float* dghn, void* stream);
+/* The two scans with the hidden size U as an argument: U = 32 is tpgsr_bigru_fwd / tpgsr_bigru_bwd themselves, U = 64 (TSRN / TSRN_TL with
+ * hidden_units = 64) runs one wavefront per (sequence, direction), two per workgroup.  gi / dgi / dgh [P][6U], column = dir*3U + gate*U + j;
+ * h_out / dh_out [P][2U], column = dir*U + j; gates [P][8U], column = dir*4U + q*U + j; w_hh [2][3U][U], b_hh [2][3U].  Any other U is an
+ * argument error; N H W 8U must stay below 2^31 (32-bit indices). */
+int tpgsr_bigru_fwd_u(const float* gi, const float* w_hh, const float* b_hh, int N, int H, int W, int axis, int hidden,
+                      float* h_out, float* gates /* [P][8U] or NULL */, void* stream);
+int tpgsr_bigru_bwd_u(const float* gates, const float* h_out, const float* dh_out, const float* dh_out2, const float* w_hh,
+                      int N, int H, int W, int axis, int hidden, float* dgi, float* dgh, void* stream);
 /* test hook: the recurrence's own sigmoid / tanh (csrc/gru.hip: compensated v_exp_f32, v_rcp_f32 + one Newton step) over n values */
 int tpgsr_gru_gate_math_probe(const float* x, float* sg, float* th, int n, void* stream);
 /* ALL weight gradients of one GruBlock in one launch (csrc/gru_wgrad.hip; model/tsrn.py:491-508, the backward pass of GruBlock.forward):
@@ -514,7 +522,8 @@ typedef struct tpgsr_gru_wgrad_args {
 } tpgsr_gru_wgrad_args;
 int tpgsr_gru_wgrad_splits(long long P);
 int tpgsr_gru_wgrad(const tpgsr_gru_wgrad_args* w, void* stream);
-/* look-ahead, in time steps, of the operand prefetch rings of tpgsr_bigru_fwd / _bwd: 4, 8 (default) or 12 (TPGSR_GRU_PF); speed only */
+/* look-ahead, in time steps, of the operand prefetch rings of tpgsr_bigru_fwd / _bwd: 4, 8 (default) or 12 (TPGSR_GRU_PF); speed only
+ * (the 64-unit scans run a setting of 12 with 8: their 192 weight registers leave no room for a 12-step ring) */
 void tpgsr_gru_set_prefetch(int steps);
 
 /* ------------------------------------------------------------------------------------------------

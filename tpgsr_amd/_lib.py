@@ -157,6 +157,8 @@ _SIGS = {
     "tpgsr_bigru_fwd": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
     "tpgsr_bigru_bwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
     "tpgsr_bigru_bwd2": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]),
+    "tpgsr_bigru_fwd_u": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
+    "tpgsr_bigru_bwd_u": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp]),
     "tpgsr_gru_gate_math_probe": (ci, [vp, vp, vp, ci, vp]),
     "tpgsr_gru_wgrad_splits": (ci, [ll]),
     "tpgsr_gru_wgrad": (ci, [C.POINTER(GruWgradArgs), vp]),

@@ -385,12 +385,12 @@ class BNLayer:
 
 
 class GruLayer:
-    """GruBlock (model/tsrn.py:491-508): 1x1 conv -> bidirectional GRU(hidden 32) along one spatial axis.
+    """GruBlock (model/tsrn.py:491-508): 1x1 conv -> bidirectional GRU(hidden Hd = 32 or 64) along one spatial axis.
     axis 0: sequences along W (gru2); axis 1: along H (gru1, the reference's transpose(-1,-2)).
 
     The 1x1 conv and the GRU's input projection are two linear maps back to back, so they run as ONE MFMA conv with the
     composed operand Wc = W_ih W_1, bc = W_ih b_1 + b_ih (rebuilt from the parameters every step by the pack program):
-    the intermediate 64-channel map of the reference never exists, in either direction.  The gradients of W_1, b_1,
+    the intermediate 2 Hd-channel map of the reference never exists, in either direction.  The gradients of W_1, b_1,
     W_ih, b_ih follow from dWc / dbc by the chain rule (tpgsr_compose_bwd_program, once per backward pass)."""
 
     def __init__(self, eng, prefix: str, axis: int):
@@ -401,44 +401,45 @@ class GruLayer:
         self.U, self.Cin = W1.shape[0], W1.shape[1]
         gp = prefix + ".gru."
         self.gp = gp
-        hid = P[gp + "weight_hh_l0"].shape[1]
-        if hid != 32:
-            raise NotImplementedError("the fused BiGRU kernel is specialised for hidden_units=32 (the reference default)")
+        self.Hd = Hd = P[gp + "weight_hh_l0"].shape[1]      # hidden size; gi / dgi / dgh [P][6 Hd], h [P][2 Hd], gates [P][8 Hd]
+        K.check_gru_hidden(Hd)
+        self.G = G = 3 * Hd                                 # gate rows of one direction
         assert P[gp + "weight_ih_l0"].shape[1] == self.U and self.U % 4 == 0 and self.Cin % 4 == 0
         Cin = self.Cin
-        self.wc_f = torch.empty(Cin, 192, dtype=F32, device=dev)    # forward operand [K=Cin][192]
-        self.wc_d = torch.empty(192, Cin, dtype=F32, device=dev)    # dgrad operand  [K'=192][Cin]
-        self.bc = torch.empty(192, dtype=F32, device=dev)
-        self.whh = torch.empty(2, 96, 32, dtype=F32, device=dev)
-        self.bhh = torch.empty(2, 96, dtype=F32, device=dev)
+        self.wc_f = torch.empty(Cin, 2 * G, dtype=F32, device=dev)    # forward operand [K=Cin][6 Hd]
+        self.wc_d = torch.empty(2 * G, Cin, dtype=F32, device=dev)    # dgrad operand  [K'=6 Hd][Cin]
+        self.bc = torch.empty(2 * G, dtype=F32, device=dev)
+        self.whh = torch.empty(2, G, Hd, dtype=F32, device=dev)
+        self.bhh = torch.empty(2, G, dtype=F32, device=dev)
         for d, suf in enumerate(("", "_reverse")):
             wih = P[gp + "weight_ih_l0" + suf]
-            eng.add_pack(wih, self.wc_f, self.wc_d, Cout=96, Cin=Cin, KH=self.U, KW=1, kind=5, f_ld=192, f_coff=d * 96,
-                         src2=W1, numel=96 * Cin)
-            eng.add_pack(wih, self.bc, None, Cout=96, Cin=0, KH=self.U, KW=1, kind=6, f_coff=d * 96, src2=P[self.b1name],
-                         src3=P[gp + "bias_ih_l0" + suf], numel=96)
+            eng.add_pack(wih, self.wc_f, self.wc_d, Cout=G, Cin=Cin, KH=self.U, KW=1, kind=5, f_ld=2 * G, f_coff=d * G,
+                         src2=W1, numel=G * Cin)
+            eng.add_pack(wih, self.bc, None, Cout=G, Cin=0, KH=self.U, KW=1, kind=6, f_coff=d * G, src2=P[self.b1name],
+                         src3=P[gp + "bias_ih_l0" + suf], numel=G)
             eng.add_pack(P[gp + "weight_hh_l0" + suf], self.whh[d], None, kind=2)
             eng.add_pack(P[gp + "bias_hh_l0" + suf], self.bhh[d], None, kind=2)
         eng.register_operand(self.wc_f, self.wc_d)
 
     def fwd(self, N, H, W, x, gi, h, gates=None, **loader):
         """gi = loader(x) Wc^T + bc; h = BiGRU(gi) (gates: saved for bwd in training plans).  ONE launch (csrc/gru_proj.hip: the
-        projection goes from the matrix cores into LDS, `gi` is not touched) when the block is that kernel's, else projection + scan;
-        gi: the [P][192] workspace or a callable returning it (only called when it is needed)"""
-        g = ConvGeom(N, H, W, self.Cin, 192)
+        projection goes from the matrix cores into LDS, `gi` is not touched) when the block is that kernel's (hidden size 32 only), else
+        projection + scan; gi: the [P][6 Hd] workspace or a callable returning it (only called when it is needed)"""
+        g = ConvGeom(N, H, W, self.Cin, 2 * self.G)
         pa = K.make_bigru_proj_args(K.make_conv_args(g, x, self.wc_f, None, bias=self.bc, **loader), self.whh, self.bhh, self.axis, h, gates)
-        if K.bigru_proj_supported(pa):
+        if K.bigru_proj_supported(pa, self.Hd):
             K.bigru_proj_fwd(pa)
             return
         gi = gi() if callable(gi) else gi
         K.conv_fwd(K.make_conv_args(g, x, self.wc_f, gi, bias=self.bc, **loader))
-        K.bigru_fwd(gi, self.whh, self.bhh, N, H, W, self.axis, h, gates)
+        K.bigru_fwd(gi, self.whh, self.bhh, N, H, W, self.axis, h, gates, hidden=self.Hd)
 
     def bwd(self, N, H, W, x, gates, h, dh, dh2, dgi, dgh, dx, dx_bnb=None, **loader):
         """all parameter gradients of the block + dx = dL/d loader(x) (dx None: the caller takes it from dgi / wc_d);
         dx_bnb: BNLayer.fuse_stats(...) of the BatchNorm dx is the incoming gradient of"""
         eng, G, gp = self.eng, self.eng.G, self.gp
-        if K.gru_wgrad_fused():
+        Hd, Gd = self.Hd, self.G
+        if K.gru_wgrad_fused(Hd):      # (a 32-unit kernel: the literals below are its shapes)
             # ONE weight-gradient launch for the whole block (csrc/gru_wgrad.hip): back-propagation through time writes dgi and only the
             # n-gate plane of the hidden-side gradient (`dgh` is used as [P][64]); loader(x), h, dgi, dghn are each read once
             P = N * H * W
@@ -462,28 +463,28 @@ class GruLayer:
             if dx is not None:
                 K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, 192, self.Cin), dgi, self.wc_d, dx, bnb=dx_bnb))
             return
-        K.bigru_bwd(gates, h, dh, dh2, self.whh, N, H, W, self.axis, dgi, dgh)
+        K.bigru_bwd(gates, h, dh, dh2, self.whh, N, H, W, self.axis, dgi, dgh, hidden=Hd)
         with K.side():
             for d, suf in enumerate(("", "_reverse")):
                 sgn = 1 if d == 0 else -1
                 # hidden side: dW_hh[d] = dgh[:, d]^T h_prev(d), h_prev = h shifted one step against the scan direction
-                gh = ConvGeom(N, H, W, 32, 96, 1, 1, sgn if self.axis == 1 else 0, sgn if self.axis == 0 else 0, H, W)
-                Z = K.wgrad_splits(gh.M, gh.K, 96)
-                part, dbp = eng.wgrad_buffers(Z * 32 * 96, Z * 96)
-                ca = K.make_conv_args(gh, h, in_ld=64, in_coff=32 * d)
-                K.conv_wgrad(K.make_wgrad_args(ca, dgh, part, dbp, dy_ld=192, dy_coff=96 * d))
+                gh = ConvGeom(N, H, W, Hd, Gd, 1, 1, sgn if self.axis == 1 else 0, sgn if self.axis == 0 else 0, H, W)
+                Z = K.wgrad_splits(gh.M, gh.K, Gd)
+                part, dbp = eng.wgrad_buffers(Z * Hd * Gd, Z * Gd)
+                ca = K.make_conv_args(gh, h, in_ld=2 * Hd, in_coff=Hd * d)
+                K.conv_wgrad(K.make_wgrad_args(ca, dgh, part, dbp, dy_ld=2 * Gd, dy_coff=Gd * d))
                 K.wgrad_reduce(part, dbp, Z, gh, G[gp + "weight_hh_l0" + suf], G[gp + "bias_hh_l0" + suf], accumulate=True)
             # input side, both directions at once: dWc = dgi^T loader(x), dbc = colsum(dgi); chain rule at the end of the pass
-            gc = ConvGeom(N, H, W, self.Cin, 192)
-            Z = K.wgrad_splits(gc.M, gc.K, 192)
-            part, dbp = eng.wgrad_buffers(Z * self.Cin * 192, Z * 192)
+            gc = ConvGeom(N, H, W, self.Cin, 2 * Gd)
+            Z = K.wgrad_splits(gc.M, gc.K, 2 * Gd)
+            part, dbp = eng.wgrad_buffers(Z * self.Cin * 2 * Gd, Z * 2 * Gd)
             K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(gc, x, **loader), dgi, part, dbp))
             ws = eng._cur_ws
-            dWc, dbc = ws("dWc_" + self.prefix, 192, self.Cin), ws("dbc_" + self.prefix, 192)
+            dWc, dbc = ws("dWc_" + self.prefix, 2 * Gd, self.Cin), ws("dbc_" + self.prefix, 2 * Gd)
             K.wgrad_reduce(part, dbp, Z, gc, dWc, dbc, accumulate=False)
             eng._compose.append((self, dWc, dbc))
         if dx is not None:
-            K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, 192, self.Cin), dgi, self.wc_d, dx, bnb=dx_bnb))
+            K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, 2 * Gd, self.Cin), dgi, self.wc_d, dx, bnb=dx_bnb))
 
 
 class TConvStrip:
@@ -623,8 +624,8 @@ class _EngineBase:
             for k, v in t.items():
                 setattr(d, k, v.data_ptr())
             keep += list(t.values())
-            d.Cin, d.U, d.G, d.blk0 = L.Cin, L.U, 96, blk
-            blk += lib.tpgsr_compose_bwd_blocks(L.Cin, L.U, 96)
+            d.Cin, d.U, d.G, d.blk0 = L.Cin, L.U, L.G, blk
+            blk += lib.tpgsr_compose_bwd_blocks(L.Cin, L.U, L.G)
         table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
         if K._REC is not None:
             K._REC.keep += keep
@@ -969,9 +970,10 @@ class TSRNEngine(_EngineBase):
             t = f"r{i}_"
             y1, y2 = ws(t + "y1", P1, Cc), ws(t + "y2", P1, Cc)
             h1, out = ws(t + "h1", P1, Cc), ws(t + "out", P1, Cc)
-            gi1, gi2 = (lambda t=t: ws(t + "gi1", P1, 192)), (lambda t=t: ws(t + "gi2", P1, 192))      # only without the one-launch GruBlock
-            gt1 = ws(t + "gt1", P1, 256) if training else None      # GRU gate values, kept for back-propagation
-            gt2 = ws(t + "gt2", P1, 256) if training else None
+            G2 = 2 * L["gru1"].G                        # gate columns of both directions: 6 x hidden size (192 by default)
+            gi1, gi2 = (lambda t=t: ws(t + "gi1", P1, G2)), (lambda t=t: ws(t + "gi2", P1, G2))      # only without the one-launch GruBlock
+            gt1 = ws(t + "gt1", P1, 4 * Cc) if training else None      # GRU gate values [P][8 x hidden], kept for back-propagation
+            gt2 = ws(t + "gt2", P1, 4 * Cc) if training else None
             part, _ = L["bn1"].partial(P1)
             fin = L["bn1"].fin(P1, L["conv1"].b) if training else None      # finalized by the convolution's own launch
             g1 = L["conv1"].fwd(N, H, W, cur, y1, bn_partial=part if training else None, bn_fin=fin, bn_coarse=training)
@@ -1146,26 +1148,27 @@ class TSRNEngine(_EngineBase):
             if (self.srb - 1 - i) % nbb == 0 and not leaf0:
                 sb = K.side_batch_begin()   # one fork per block (or per nbb blocks) instead of four
             p = f"r{i}_"
-            dgi, dgh = buf("dgi", p + "g2_", 192), buf("dgh", p + "g2_", 192)
+            G2 = 2 * L["gru1"].G                    # gate columns of both directions (192 by default)
+            dgi, dgh = buf("dgi", p + "g2_", G2), buf("dgh", p + "g2_", G2)
             X = t[f"r{i - 1}_out"] if i > 0 else t["b1"]
             y1, y2, gt1, h1, gt2, out = (t[p + n] for n in ("y1", "y2", "gt1", "h1", "gt2", "out"))
             # gru2 (input X + h1): parameter grads + d(X + h1) -> gA (incoming gA/gB are dead after the scan)
             L["gru2"].bwd(N, H, W, X, gt2, out, gA, gB if have_B else None, dgi, dgh, gA, in2=h1)
             # gru1 (input bn2(y2) [+ text strip]): dh = gA
-            dgi, dgh = buf("dgi", p + "g1_", 192), buf("dgh", p + "g1_", 192)
+            dgi, dgh = buf("dgi", p + "g1_", G2), buf("dgh", p + "g1_", G2)
             # (leaf0: block 0's BatchNorm backward runs on the leaf stream, its producer here -- no shared scratch across streams)
-            fz2 = None if leaf0 else L["bn2"].fuse_stats(y2, P1, "none", 192)
+            fz2 = None if leaf0 else L["bn2"].fuse_stats(y2, P1, "none", G2)
             if self.tl:
                 g1 = L["gru1"]
                 g1.bwd(N, H, W, y2, gt1, h1, gA, None, dgi, dgh, None, in_b=t["temb"], cin_a=Cc, **L["bn2"].loader)
                 # data gradient of the composed 96->192 projection in two column blocks: image features and text strip
-                K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, 192, Cc), dgi, g1.wc_d, da, wt_ld=g1.Cin, wt_coff=0, bnb=fz2))
+                K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, G2, Cc), dgi, g1.wc_d, da, wt_ld=g1.Cin, wt_coff=0, bnb=fz2))
                 # the text strip's share of the gradient (summed over the H rows it was broadcast to, accumulated over the blocks) only meets
                 # the caller's stream again at the InfoGen backward pass: it runs on the leaf stream (idle until the STN head's backward),
                 # block after block in order, next to the rest of this block on the caller's stream (round 5: -18 us per block there)
                 with (K.leaf() if self.leaf_strip else contextlib.nullcontext()):
                     dtb = ws("d_tb", P1, self.Ct)
-                    K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, 192, self.Ct), dgi, g1.wc_d, dtb, wt_ld=g1.Cin, wt_coff=Cc))
+                    K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, G2, self.Ct), dgi, g1.wc_d, dtb, wt_ld=g1.Cin, wt_coff=Cc))
                     K.hsum(dtb, N, H, W, self.Ct, ws("dtemb", N * W, self.Ct), accumulate=(i != self.srb - 1))
             else:
                 L["gru1"].bwd(N, H, W, y2, gt1, h1, gA, None, dgi, dgh, da, dx_bnb=fz2, **L["bn2"].loader)

@@ -548,7 +548,7 @@ def mean_over_height(x):
 
 # ---- bidirectional GRU over one spatial axis (GruBlock, model/tsrn.py:491-508) --------------------------------------------
 class _GruProj(torch.autograd.Function):
-    """gi [N][H][W][192] = x W_ih^T + b_ih for both directions (two MFMA 1x1 convs into the two column halves)"""
+    """gi [N][H][W][6U] = x W_ih^T + b_ih for both directions (two MFMA 1x1 convs into the two column halves; U = hidden size)"""
 
     @staticmethod
     def forward(ctx, x, w0, w1, b0, b1):
@@ -592,48 +592,54 @@ class _GruProj(torch.autograd.Function):
 
 
 class _GruCore(torch.autograd.Function):
+    """h [N][H][W][2U] = BiGRU scan over gi [N][H][W][6U]; U from weight_hh_l0's shape [3U][U] (32 or 64: kernels.GRU_HIDDEN)"""
+
     @staticmethod
     def forward(ctx, gi, whh0, whh1, bhh0, bhh1, axis):
         _chk(gi, whh0, whh1, bhh0, bhh1)
         gi = _c(gi)
         N, H, W, G2 = gi.shape
-        if G2 != 192 or whh0.shape != (96, 32):
-            raise NotImplementedError("the fused BiGRU kernel is specialised for hidden size 32 (the reference's hidden_units)")
+        U = whh0.shape[1]
+        K.check_gru_hidden(U)          # (the refusal comes from the host, before anything is launched)
+        if G2 != 6 * U or tuple(whh0.shape) != (3 * U, U) or tuple(whh1.shape) != (3 * U, U):
+            raise ValueError(f"BiGRU scan: gi has {G2} columns and weight_hh is {tuple(whh0.shape)}; expected {6 * U} and ({3 * U}, {U})")
         dev = gi.device
-        whh = torch.empty(2, 96, 32, device=dev)
-        bhh = torch.empty(2, 96, device=dev)
+        whh = torch.empty(2, 3 * U, U, device=dev)
+        bhh = torch.empty(2, 3 * U, device=dev)
         for d, (w, b) in enumerate(((whh0, bhh0), (whh1, bhh1))):
-            K.copy(_c(w), whh[d], 96 * 32)
-            K.copy(_c(b), bhh[d], 96)
-        h = _new(gi, N, H, W, 64)
-        gates = _new(gi, N, H, W, 256)
-        K.bigru_fwd(gi, whh, bhh, N, H, W, axis, h, gates)
+            K.copy(_c(w), whh[d], 3 * U * U)
+            K.copy(_c(b), bhh[d], 3 * U)
+        h = _new(gi, N, H, W, 2 * U)
+        gates = _new(gi, N, H, W, 8 * U)
+        K.bigru_fwd(gi, whh, bhh, N, H, W, axis, h, gates, hidden=U)
         ctx.save_for_backward(gates, h, whh)
-        ctx.cfg = (N, H, W, axis)
+        ctx.cfg = (N, H, W, axis, U)
         return h
 
     @staticmethod
     def backward(ctx, dh):
         gates, h, whh = ctx.saved_tensors
-        N, H, W, axis = ctx.cfg
-        dgi, dgh = _new(h, N, H, W, 192), _new(h, N, H, W, 192)
-        K.bigru_bwd(gates, h, _c(dh), None, whh, N, H, W, axis, dgi, dgh)
+        N, H, W, axis, U = ctx.cfg
+        dgi, dgh = _new(h, N, H, W, 6 * U), _new(h, N, H, W, 6 * U)
+        K.bigru_bwd(gates, h, _c(dh), None, whh, N, H, W, axis, dgi, dgh, hidden=U)
         res = []
         for d in range(2):
             sgn = 1 if d == 0 else -1
             # dW_hh[d] = dgh[:, d]^T h_prev(d): h shifted one step against the scan direction (engine.GruLayer.bwd)
-            gh = ConvGeom(N, H, W, 32, 96, 1, 1, sgn if axis == 1 else 0, sgn if axis == 0 else 0, H, W)
-            Z = K.wgrad_splits(gh.M, gh.K, 96)
-            part, dbp = _new(h, Z, 32, 96), _new(h, Z, 96)
-            K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(gh, h, in_ld=64, in_coff=32 * d), dgh, part, dbp, dy_ld=192, dy_coff=96 * d))
-            dw, db = _new(h, 96, 32), _new(h, 96)
+            gh = ConvGeom(N, H, W, U, 3 * U, 1, 1, sgn if axis == 1 else 0, sgn if axis == 0 else 0, H, W)
+            Z = K.wgrad_splits(gh.M, gh.K, 3 * U)
+            part, dbp = _new(h, Z, U, 3 * U), _new(h, Z, 3 * U)
+            K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(gh, h, in_ld=2 * U, in_coff=U * d), dgh, part, dbp, dy_ld=6 * U, dy_coff=3 * U * d))
+            dw, db = _new(h, 3 * U, U), _new(h, 3 * U)
             K.wgrad_reduce(part, dbp, Z, gh, dw, db, accumulate=False)
             res.append((dw, db))
         return dgi, res[0][0], res[1][0], res[0][1], res[1][1], None
 
 
 def bigru(x, gru, axis: int):
-    """bidirectional GRU (hidden 32) along W (axis 0) or H (axis 1) of an NHWC map; gru: a GRUParams holder"""
+    """bidirectional GRU (hidden size U = 32 or 64, read from weight_hh_l0) along W (axis 0) or H (axis 1) of an NHWC map;
+    gru: a GRUParams holder.  Returns [N][H][W][2U]."""
+    K.check_gru_hidden(gru.weight_hh_l0.shape[1])
     gi = _GruProj.apply(x, gru.weight_ih_l0, gru.weight_ih_l0_reverse, gru.bias_ih_l0, gru.bias_ih_l0_reverse)
     return _GruCore.apply(gi, gru.weight_hh_l0, gru.weight_hh_l0_reverse, gru.bias_hh_l0, gru.bias_hh_l0_reverse, axis)
 

@@ -1049,9 +1049,23 @@ def reduce_partials(part, Z, n, out, accumulate=True):
 
 
 # ---- GRU ------------------------------------------------------------------------------------------------------
-def bigru_fwd(gi, w_hh, b_hh, N, H, W, axis, h_out, gates=None):
-    """gates [P][256]: (r, z, n, W_hn h + b_hn) per direction, stored for bigru_bwd (None at inference)"""
-    _launch("tpgsr_bigru_fwd", _p(gi), _p(w_hh), _p(b_hh), N, H, W, axis, _p(h_out), _p(gates))
+GRU_HIDDEN = (32, 64)      # hidden sizes the BiGRU scans are built for (csrc/gru.hip)
+
+
+def check_gru_hidden(hidden: int):
+    """the refusal comes from the host: no launch for a hidden size the scans are not built for"""
+    if hidden not in GRU_HIDDEN:
+        raise NotImplementedError(f"the fused BiGRU kernels are specialised for hidden size 32 or 64 (the reference's hidden_units; got {hidden})")
+
+
+def bigru_fwd(gi, w_hh, b_hh, N, H, W, axis, h_out, gates=None, hidden=32):
+    """gi [P][6U], h_out [P][2U]; gates [P][8U]: (r, z, n, W_hn h + b_hn) per direction, stored for bigru_bwd (None at inference).
+    U = hidden: 32 (tpgsr_bigru_fwd) or 64 (tpgsr_bigru_fwd_u)"""
+    check_gru_hidden(hidden)
+    if hidden == 32:
+        _launch("tpgsr_bigru_fwd", _p(gi), _p(w_hh), _p(b_hh), N, H, W, axis, _p(h_out), _p(gates))
+    else:
+        _launch("tpgsr_bigru_fwd_u", _p(gi), _p(w_hh), _p(b_hh), N, H, W, axis, hidden, _p(h_out), _p(gates))
 
 
 def make_bigru_proj_args(cargs: ConvArgs, w_hh, b_hh, axis, h_out, gates=None) -> "_lib.BigruProjArgs":
@@ -1062,17 +1076,22 @@ def make_bigru_proj_args(cargs: ConvArgs, w_hh, b_hh, axis, h_out, gates=None) -
     return a
 
 
-def bigru_proj_supported(pargs) -> bool:
-    """does the one-launch GruBlock forward (csrc/gru_proj.hip) take this block under the current arithmetic policy?"""
-    return bool(_lib.load().tpgsr_bigru_proj_supported(C.byref(pargs)))
+def bigru_proj_supported(pargs, hidden=32) -> bool:
+    """does the one-launch GruBlock forward (csrc/gru_proj.hip, hidden size 32 only) take this block under the current arithmetic policy?"""
+    return hidden == 32 and bool(_lib.load().tpgsr_bigru_proj_supported(C.byref(pargs)))
 
 
 def bigru_proj_fwd(pargs):
     _launch("tpgsr_bigru_proj_fwd", C.byref(pargs))
 
 
-def bigru_bwd(gates, h_out, dh_out, dh_out2, w_hh, N, H, W, axis, dgi, dgh):
-    _launch("tpgsr_bigru_bwd", _p(gates), _p(h_out), _p(dh_out), _p(dh_out2), _p(w_hh), N, H, W, axis, _p(dgi), _p(dgh))
+def bigru_bwd(gates, h_out, dh_out, dh_out2, w_hh, N, H, W, axis, dgi, dgh, hidden=32):
+    """dgi / dgh [P][6U]; U = hidden: 32 (tpgsr_bigru_bwd) or 64 (tpgsr_bigru_bwd_u)"""
+    check_gru_hidden(hidden)
+    if hidden == 32:
+        _launch("tpgsr_bigru_bwd", _p(gates), _p(h_out), _p(dh_out), _p(dh_out2), _p(w_hh), N, H, W, axis, _p(dgi), _p(dgh))
+    else:
+        _launch("tpgsr_bigru_bwd_u", _p(gates), _p(h_out), _p(dh_out), _p(dh_out2), _p(w_hh), N, H, W, axis, hidden, _p(dgi), _p(dgh))
 
 
 def bigru_bwd2(gates, h_out, dh_out, dh_out2, w_hh, N, H, W, axis, dgi, dghn):
@@ -1085,8 +1104,9 @@ def bigru_bwd2(gates, h_out, dh_out, dh_out2, w_hh, N, H, W, axis, dgi, dghn):
 GRU_WGRAD = os.environ.get("TPGSR_GRU_WGRAD", "1") != "0"
 
 
-def gru_wgrad_fused() -> bool:
-    return bool(GRU_WGRAD and CONV_TERMS)
+def gru_wgrad_fused(hidden=32) -> bool:
+    """(csrc/gru_wgrad.hip is a 32-unit kernel: other hidden sizes take bigru_bwd + conv_wgrad + wgrad_reduce)"""
+    return bool(GRU_WGRAD and CONV_TERMS and hidden == 32)
 
 
 def gru_wgrad_splits(P: int) -> int:
