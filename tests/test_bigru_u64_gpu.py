@@ -1,4 +1,4 @@
-"""The 64-unit bidirectional GRU (`Fh.bigru` with weight_hh_l0 [192][64]: csrc/gru.hip, bigru_fwd_u64_kernel / bigru_bwd_u64_kernel) against
+"""The 64-unit bidirectional GRU (`Fh.bigru` with weight_hh_l0 [192][64]: csrc/gru.hip, bigru_fwd_kernel<64> / bigru_bwd_kernel<64>) against
 torch.nn.GRU(Cin, 64, bidirectional=True, batch_first=True) in float64 on the CPU, element by element.
 
 Method and bounds are those of tests/test_functional_ops_gpu.py (its Case record, run_reference / run_gpu / err and CONV_LIMITS are imported,

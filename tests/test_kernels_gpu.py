@@ -530,6 +530,41 @@ def test_bigru_fwd_bwd(axis, N, H, W):
         assert relerr(dw.cpu(), p["g.weight_hh_l0" + suf].grad) < 2e-5, (d, relerr(dw.cpu(), p["g.weight_hh_l0" + suf].grad))
 
 
+@pytest.mark.parametrize("axis", [0, 1])
+@pytest.mark.parametrize("N,H,W", [(2, 3, 5), (1, 2, 8), (2, 16, 9)])
+def test_bigru_bwd_compact_is_full(axis, N, H, W):
+    """The compact back-propagation (bigru_bwd2: dghn [P][64]) is a flag on the kernel of the full one (bigru_bwd: dgh [P][192]): on the
+    same operands both write the same registers, so dgi is equal bit for bit, dghn is the n plane of dgh, and the r / z planes of dgh
+    are dgi's.  Scan lengths with the default look-ahead of 8: shorter than the ring (5, 3, 2: the bounds-tested kernel), one whole
+    group (8), two whole groups (16), and a partial refill of the ring (9)."""
+    k = K()
+    g = torch.Generator().manual_seed(61 + axis)
+    P = N * H * W
+    R = lambda *s: torch.randn(*s, generator=g).to(DEV)
+    gi, whh, bhh = R(P, 192), R(2, 96, 32) / 32 ** 0.5, R(2, 96)
+    dh, dh2 = R(P, 64), R(P, 64)
+    h, gates = torch.empty(P, 64, device=DEV), torch.empty(P, 256, device=DEV)
+    k.bigru_fwd(gi, whh, bhh, N, H, W, axis, h, gates)
+    nan = lambda c: torch.full((P, c), float("nan"), device=DEV)
+    dgi, dgh, dgi2, dghn = nan(192), nan(192), nan(192), nan(64)
+    k.bigru_bwd(gates, h, dh, dh2, whh, N, H, W, axis, dgi, dgh)
+    k.bigru_bwd2(gates, h, dh, dh2, whh, N, H, W, axis, dgi2, dghn)
+    torch.cuda.synchronize()
+    assert not torch.isnan(dgi).any() and not torch.isnan(dgh).any()
+    assert torch.equal(dgi2, dgi)
+    assert torch.equal(dghn, dgh.view(P, 2, 3, 32)[:, :, 2, :].reshape(P, 64))
+    assert torch.equal(dgh.view(P, 2, 3, 32)[:, :, :2, :], dgi.view(P, 2, 3, 32)[:, :, :2, :])
+    # ... and without a second gradient (the other branch of the shared operand fetch)
+    dgi, dgh, dgi2, dghn = nan(192), nan(192), nan(192), nan(64)
+    k.bigru_bwd(gates, h, dh, None, whh, N, H, W, axis, dgi, dgh)
+    k.bigru_bwd2(gates, h, dh, None, whh, N, H, W, axis, dgi2, dghn)
+    torch.cuda.synchronize()
+    assert not torch.isnan(dgi).any() and not torch.isnan(dgh).any()
+    assert torch.equal(dgi2, dgi)
+    assert torch.equal(dghn, dgh.view(P, 2, 3, 32)[:, :, 2, :].reshape(P, 64))
+    assert torch.equal(dgh.view(P, 2, 3, 32)[:, :, :2, :], dgi.view(P, 2, 3, 32)[:, :, :2, :])
+
+
 def test_tps_and_grid_sample(golden_dir):
     import os
     k = K()

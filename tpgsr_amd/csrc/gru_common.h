@@ -1,14 +1,14 @@
 // Device code shared by the BiGRU kernels (gru.hip: the scans over precomputed input projections and back-propagation through time;
 // gru_proj.hip: the forward scan with the GruBlock's input projection computed in the same launch): sequence geometry, the gate
-// functions of the recurrence, packed-FMA helpers.  GruBlock: model/tsrn.py:491-508.
+// functions of the recurrence, packed-FMA helpers and -- at the end of the file -- the time step itself, forward and backward, for every
+// kernel that runs it.  GruBlock: model/tsrn.py:491-508.
 #pragma once
 #include "common.h"
 
-#define GRU_H 32
-// one wavefront per workgroup: the per-step barrier degenerates to wave-local ordering
+#define GRU_H 32      // the hidden size of the files that are built for one size only (gru_proj.hip, gru_wgrad.hip)
 
 struct SeqGeom {
-  int base;    // pixel index of t = 0 (32-bit: the launchers bound N H W 256 by 2^31 -- 64-bit multiplies were ~20 instructions of a step)
+  int base;    // pixel index of t = 0 (32-bit: the launchers bound N H W 8 U, the largest index, by 2^31 -- 64-bit multiplies were ~20 instructions of a step)
   int stride;  // pixel stride between time steps
   int T;
   bool active;
@@ -106,4 +106,105 @@ __device__ __forceinline__ float gru_tanh(float x) {
   float small = x * p;
   asm volatile("" : "+v"(small), "+v"(big));
   return fabsf(x) < 0.35f ? small : copysignf(big, x);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// The recurrence, once.  U = hidden size (32 | 64).
+// ------------------------------------------------------------------------------------------------------
+// Lane maps.  A scanning wave exchanges per-unit values through wave-private, parity-double-buffered LDS slots: State = one float per
+// unit (the hidden state; dghn), Pairs = two (dr, dz).  put() = where this lane writes its own, get() = where its direction's vector starts.
+//   U = 32: one wavefront per sequence, lanes 0-31 the forward direction, 32-63 the reverse one; State [parity][dir * 32 + unit]
+//           (put() indexes with the lane id itself: the compiler does not see that d * 32 + j is the same number).
+//   U = 64: one wavefront per (sequence, direction), two per workgroup (wave 0 forward, wave 1 reverse), independent recurrences: nothing
+//           ever waits for the other wave, no workgroup barrier anywhere; State [dir][parity][unit].
+// The slots are declared with these array types, not as flat floats: the index form decides the address arithmetic of every step.
+// Either way a slot belongs to ONE wave, whose LDS operations execute in order: the per-step barrier is a compiler barrier only.
+template <int U>
+struct GruLanes;
+template <>
+struct GruLanes<32> {
+  static constexpr int THREADS = 64;
+  typedef float State[2][64];         // [parity][dir * 32 + unit]
+  typedef float Pairs[2][2][64];      // [parity][dir][unit][2]
+  int lane, d, j;      // d = direction, j = hidden unit
+  __device__ __forceinline__ GruLanes(unsigned tid) : lane(tid & 63), d(lane >> 5), j(lane & 31) {}
+  __device__ __forceinline__ float* put(State& s, int parity) const { return &s[parity][lane]; }
+  __device__ __forceinline__ const float4* get(const State& s, int parity) const { return reinterpret_cast<const float4*>(&s[parity][d * 32]); }
+  __device__ __forceinline__ float2* put(Pairs& s, int parity) const { return reinterpret_cast<float2*>(&s[parity][d][2 * j]); }
+  __device__ __forceinline__ const float4* get(const Pairs& s, int parity) const { return reinterpret_cast<const float4*>(&s[parity][d][0]); }
+};
+template <>
+struct GruLanes<64> {
+  static constexpr int THREADS = 128;
+  typedef float State[2][2][64];      // [dir][parity][unit]
+  typedef float Pairs[2][2][128];     // [dir][parity][unit][2]
+  int d, j;
+  __device__ __forceinline__ GruLanes(unsigned tid) : d(__builtin_amdgcn_readfirstlane(tid >> 6)), j(tid & 63) {}      // (d: wave-uniform)
+  __device__ __forceinline__ float* put(State& s, int parity) const { return &s[d][parity][j]; }
+  __device__ __forceinline__ const float4* get(const State& s, int parity) const { return reinterpret_cast<const float4*>(&s[d][parity][0]); }
+  __device__ __forceinline__ float2* put(Pairs& s, int parity) const { return reinterpret_cast<float2*>(&s[d][parity][2 * j]); }
+  __device__ __forceinline__ const float4* get(const Pairs& s, int parity) const { return reinterpret_cast<const float4*>(&s[d][parity][0]); }
+};
+
+// The step's pieces are LOOP-FREE functions of scalars and register arrays; the k loops around gru_mac / gru_mac_t and the W_hh loads
+// stay in the kernels.  A function that holds an unrolled loop, or takes an f2 / float4 by value into the gate math, is simplified
+// by the compiler on its own before it is inlined and the step comes out scheduled differently (and with other register counts) than
+// the same lines written in the kernel; in this form every scan instantiation is the code of the hand-kept copies it replaced.
+
+// one k-step (state components 4k .. 4k+3) of W_hh h for one unit: six independent packed-FMA chains.  wrz = row j of W_hr / W_hz
+// interleaved (one packed FMA feeds both gates), wn2 = row j of W_hn as k-pairs; hv = the direction's state vector, a broadcast
+// ds_read_b128.  The odd components go through gru_dup_odd, NOT mk2(hv.y, hv.y) (see there).
+// Afterwards: (W_hr h, W_hz h) = (a0 + a1) + (a2 + a3), W_hn h = (n0 + n1).x + (n0 + n1).y.
+template <int U>
+__device__ __forceinline__ void gru_mac(const f2 (&wrz)[U], const f2 (&wn2)[U / 2], int k, const float4 hv, f2& a0, f2& a1, f2& a2, f2& a3,
+                                        f2& n0, f2& n1) {
+  a0 = pk_fma(wrz[4 * k], mk2(hv.x, hv.x), a0);
+  a1 = pk_fma(wrz[4 * k + 1], gru_dup_odd(hv.y), a1);
+  a2 = pk_fma(wrz[4 * k + 2], mk2(hv.z, hv.z), a2);
+  a3 = pk_fma(wrz[4 * k + 3], gru_dup_odd(hv.w), a3);
+  n0 = pk_fma(wn2[2 * k], mk2(hv.x, hv.y), n0);
+  n1 = pk_fma(wn2[2 * k + 1], mk2(hv.z, hv.w), n1);
+}
+// Gate math == nn.GRU:  r = s(gi_r + W_hr h + b_hr), z likewise, n = tanh(gi_n + r * an), an = W_hn h + b_hn, h' = (1 - z) * n + z * h.
+// wr / wz / wn = the three hidden-side products.  What back-propagation needs of a step is what this returns.
+struct GruGates {
+  float r, z, n, an;
+};
+__device__ __forceinline__ GruGates gru_gate_update(float gi_r, float gi_z, float gi_n, float wr, float wz, float wn, float br, float bz,
+                                                    float bn, float& h) {
+  GruGates q;
+  q.an = bn + wn;
+  const f2 sg = gru_sigmoid2(mk2(gi_r + (br + wr), gi_z + (bz + wz)));      // both gates in lock step
+  q.r = sg.x;
+  q.z = sg.y;
+  q.n = gru_tanh(__builtin_fmaf(q.r, q.an, gi_n));
+  h = __builtin_fmaf(q.z, h, (1.f - q.z) * q.n);      // (explicit contraction)
+  return q;
+}
+
+// back-propagation through one step: the gradients of the three gates' pre-activations from dh = d(loss) / d(h of this step), and the
+// hidden side of the n gate, dghn = dn_pre * r
+struct GruGateGrads {
+  float dr_pre, dz_pre, dn_pre, dghn;
+};
+__device__ __forceinline__ GruGateGrads gru_gate_grads(float dh, float hprev, float r, float z, float n, float an) {
+  GruGateGrads q;
+  q.dn_pre = dh * (1.f - z) * (1.f - n * n);
+  q.dz_pre = dh * (hprev - n) * z * (1.f - z);
+  q.dr_pre = q.dn_pre * an * r * (1.f - r);
+  q.dghn = q.dn_pre * r;
+  return q;
+}
+// one k-step (units 4k .. 4k+3) of W_hh^T (dr_pre, dz_pre, dghn) for one unit.  trz = column j of W_hr / W_hz interleaved, tn2 = column j
+// of W_hn as row pairs; a, b = the direction's (dr, dz) pairs of the four units, e = their dghn.
+// Afterwards: sum = ((c0 + c1) + (c2 + c3)) + (e0 + e1), dh_prev[j] = sum.x + sum.y.
+template <int U>
+__device__ __forceinline__ void gru_mac_t(const f2 (&trz)[U], const f2 (&tn2)[U / 2], int k, const float4 a, const float4 b, const float4 e,
+                                          f2& c0, f2& c1, f2& c2, f2& c3, f2& e0, f2& e1) {
+  c0 = pk_fma(trz[4 * k], mk2(a.x, a.y), c0);
+  c1 = pk_fma(trz[4 * k + 1], mk2(a.z, a.w), c1);
+  c2 = pk_fma(trz[4 * k + 2], mk2(b.x, b.y), c2);
+  c3 = pk_fma(trz[4 * k + 3], mk2(b.z, b.w), c3);
+  e0 = pk_fma(tn2[2 * k], mk2(e.x, e.y), e0);
+  e1 = pk_fma(tn2[2 * k + 1], mk2(e.z, e.w), e1);
 }

@@ -18,8 +18,8 @@
 //            sixteen time steps of a tile land in distinct bank quads).  Weight fragments come from the planes tpgsr_split_bf_program
 //            wrote for the 32x32x16 kernels ([term][n/32][k/16][lane][8]); a 16x16x32 fragment is a different 16-byte gather of the same
 //            bytes.  288 MFMAs per workgroup in two-term arithmetic (~2 us), the weights stay L2-resident.
-//   phase 3  the scan of bigru_fwd_kernel, value for value (same gate functions, same packed-FMA order), with the step's three input
-//            projections read from LDS one step ahead instead of from HBM eight steps ahead.
+//   phase 3  the scan of bigru_fwd_kernel<32>: the same step (gru_common.h's gru_mac and gru_gate_update), with the step's three
+//            input projections read from LDS one step ahead instead of from HBM eight steps ahead.
 // LDS: 64 x 196 x 4 B + 512 B per scanning wave = 49.5 / 51 KB per workgroup (three per CU = the 768 workgroups of either scan in one
 // round).  Forward only: back-propagation through time keeps its own kernels.
 //
@@ -198,8 +198,8 @@ __global__ __launch_bounds__(256) void bigru_proj_fwd_kernel(const tpgsr_bigru_p
   float* const hsw = hs + (SPW > 1 ? wave * 128 : 0);                      // this wave's exchange slot [2][64]
   const float* const giw = gi + (SPW > 1 ? wave * T * GP_RS : 0);          // ... and its rows of gi
 
-  // ---- phase 3: the scan (bigru_fwd_kernel of gru.hip, the inputs out of LDS) ----
-  const int d = lane >> 5, j = lane & 31;
+  // ---- phase 3: the scan (the step of gru_common.h, as bigru_fwd_kernel<32> of gru.hip; the inputs out of LDS) ----
+  const int d = lane >> 5, j = lane & 31;      // GruLanes<32>'s map; the slot is hsw, [parity][lane]
   f2 wrz[GRU_H], wn2[GRU_H / 2];
   {
     const float* pr = p.w_hh + ((size_t)(d * 96 + 0 * 32 + j)) * GRU_H;
@@ -236,33 +236,24 @@ __global__ __launch_bounds__(256) void bigru_proj_fwd_kernel(const tpgsr_bigru_p
     f2 a0 = mk2(0.f, 0.f), a1 = a0, a2 = a0, a3 = a0, n0 = a0, n1 = a0;
     const float4* hp = reinterpret_cast<const float4*>(&hsw[(step & 1) * 64 + d * 32]);
 #pragma unroll
-    for (int k = 0; k < GRU_H / 4; ++k) {
-      const float4 hv = hp[k];
-      a0 = pk_fma(wrz[4 * k], mk2(hv.x, hv.x), a0);
-      a1 = pk_fma(wrz[4 * k + 1], gru_dup_odd(hv.y), a1);      // (NOT mk2(hv.y, hv.y): gru_common.h)
-      a2 = pk_fma(wrz[4 * k + 2], mk2(hv.z, hv.z), a2);
-      a3 = pk_fma(wrz[4 * k + 3], gru_dup_odd(hv.w), a3);
-      n0 = pk_fma(wn2[2 * k], mk2(hv.x, hv.y), n0);
-      n1 = pk_fma(wn2[2 * k + 1], mk2(hv.z, hv.w), n1);
-    }
+    for (int k = 0; k < GRU_H / 4; ++k) gru_mac<GRU_H>(wrz, wn2, k, hp[k], a0, a1, a2, a3, n0, n1);
     const f2 rz = (a0 + a1) + (a2 + a3), nn = n0 + n1;
-    const float an = bn + (nn.x + nn.y);
-    f2 sg;
-    float n;
-    if (dbg & 32) {
-      sg = mk2(ir + (br + rz.x), iz + (bz + rz.y)) * mk2(0.25f, 0.25f);
-      n = __builtin_fmaf(sg.x, an, in_) * 0.5f;
+    GruGates q;
+    if (dbg & 32) {      // (lab: the gate functions replaced by two multiplies)
+      q.an = bn + (nn.x + nn.y);
+      const f2 sg = mk2(ir + (br + rz.x), iz + (bz + rz.y)) * mk2(0.25f, 0.25f);
+      q.r = sg.x;
+      q.z = sg.y;
+      q.n = __builtin_fmaf(q.r, q.an, in_) * 0.5f;
+      h = __builtin_fmaf(q.z, h, (1.f - q.z) * q.n);
     } else {
-      sg = gru_sigmoid2(mk2(ir + (br + rz.x), iz + (bz + rz.y)));      // both gates in lock step (gru_common.h)
-      n = gru_tanh(__builtin_fmaf(sg.x, an, in_));
+      q = gru_gate_update(ir, iz, in_, rz.x, rz.y, nn.x + nn.y, br, bz, bn, h);
     }
-    const float r = sg.x, z = sg.y;
-    h = __builtin_fmaf(z, h, (1.f - z) * n);      // (explicit: the same contraction in every kernel that runs this step)
     hsw[((step + 1) & 1) * 64 + lane] = h;
     if (!(dbg & 16)) p.h_out[pix * 64 + d * 32 + j] = h;
     if (TRAIN && !(dbg & 16)) {
-      float* q = p.gates + pix * 256 + d * 128 + j;
-      q[0] = r; q[32] = z; q[64] = n; q[96] = an;
+      float* o = p.gates + pix * 256 + d * 128 + j;
+      o[0] = q.r; o[32] = q.z; o[64] = q.n; o[96] = q.an;
     }
     pix += dpix;
     __builtin_amdgcn_wave_barrier();
