@@ -445,6 +445,10 @@ int tpgsr_prelu_bwd(const float* x, const float* alpha, const float* dy, const f
                     float* dalpha_partial, int nblk, void* stream);
 /* out = a + b (b optional scale) ; out = a*mish'(x) etc. */
 int tpgsr_add(const float* a, const float* b, long long n, float* out, void* stream);
+/* out = ((a0 + a1) + a2) + ... + a[k-1], 2 <= k <= 8 addends of n floats (a[k..7] ignored): one launch, fixed left-to-right fp32 order
+ * per element -- bitwise reproducible; 16-byte loads when every pointer is 16-byte aligned.  The gradient of a tensor with k consumers. */
+int tpgsr_add_n(const float* a0, const float* a1, const float* a2, const float* a3, const float* a4, const float* a5,
+                const float* a6, const float* a7, int k, long long n, float* out, void* stream);
 int tpgsr_act_bwd(const float* x, const float* dy, long long n, int act, float* dx, void* stream);
 int tpgsr_nchw_to_nhwc(const float* in, int N, int C, int H, int W, float* out, void* stream);
 int tpgsr_nhwc_to_nchw(const float* in, int N, int C, int H, int W, float* out, void* stream);
@@ -676,6 +680,10 @@ int tpgsr_image_loss_finalize(const float* partial, int nblk, long long n_mse, l
                               float* loss, void* stream);
 int tpgsr_image_loss_bwd(const float* out, const float* tgt, const float* dloss, int N, int C, int H, int W,
                          int gradient, float w0, float w1, float* dout, void* stream);
+/* nn.L1Loss over n elements.  fwd: partial[b] = {sum |out - tgt| of workgroup b, 0} in the image loss's [nblk][2] rows, finished by
+ * tpgsr_image_loss_finalize(partial, nblk, n, 0, w, 0, loss); bwd: dout = dloss[0] * w / n * sign(out - tgt), sign(0) = 0 */
+int tpgsr_l1_loss_fwd(const float* out, const float* tgt, long long n, float* partial, int nblk, void* stream);
+int tpgsr_l1_loss_bwd(const float* out, const float* tgt, const float* dloss, long long n, float w, float* dout, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline (dataset/dataset.py:615-632 resizeNormalize, called by alignCollate_real* :1226-1323): Pillow's 8-bit

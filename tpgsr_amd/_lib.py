@@ -150,6 +150,7 @@ _SIGS = {
     "tpgsr_prelu_fwd": (ci, [vp, vp, ll, vp, vp]),
     "tpgsr_prelu_bwd": (ci, [vp, vp, vp, vp, ll, vp, vp, ci, vp]),
     "tpgsr_add": (ci, [vp, vp, ll, vp, vp]),
+    "tpgsr_add_n": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ll, vp, vp]),
     "tpgsr_act_bwd": (ci, [vp, vp, ll, ci, vp, vp]),
     "tpgsr_nchw_to_nhwc": (ci, [vp, ci, ci, ci, ci, vp, vp]),
     "tpgsr_nhwc_to_nchw": (ci, [vp, ci, ci, ci, ci, vp, vp]),
@@ -194,6 +195,8 @@ _SIGS = {
     "tpgsr_image_loss_fwd": (ci, [vp, vp, ci, ci, ci, ci, ci, vp, ci, vp]),
     "tpgsr_image_loss_finalize": (ci, [vp, ci, ll, ll, cf, cf, vp, vp]),
     "tpgsr_image_loss_bwd": (ci, [vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, vp, vp]),
+    "tpgsr_l1_loss_fwd": (ci, [vp, vp, ll, vp, ci, vp]),
+    "tpgsr_l1_loss_bwd": (ci, [vp, vp, vp, ll, cf, vp, vp]),
     "tpgsr_sumsq_partial": (ci, [vp, ll, vp, ci, vp]),
     "tpgsr_clip_coef": (ci, [vp, ci, cf, vp, vp, vp]),
     "tpgsr_adam_step": (ci, [vp, vp, vp, vp, ll, vp, cf, cf, cf, cf, vp, vp]),

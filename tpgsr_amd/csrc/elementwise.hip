@@ -737,6 +737,54 @@ extern "C" int tpgsr_add(const float* a, const float* b, long long n, float* out
   TPGSR_LAUNCH_CHECK("tpgsr_add");
 }
 
+// out = ((a0 + a1) + a2) + ... + a[k-1], 2 <= k <= 8: the gradient of a tensor with k consumers (functional.fork) in ONE launch.  Every
+// element is summed left to right in fp32 -- plain adds, nothing for the compiler to contract or reassociate -- so the result does not
+// depend on the grid or on the vector / scalar split: bitwise the host loop `s = a0; s += a1; ...`.  16-byte loads while every pointer is
+// 16-byte aligned (n4 = n / 4 groups, else n4 = 0), the rest element by element.
+struct add_n_ptrs {
+  const float* p[8];
+};
+
+__global__ __launch_bounds__(256) void add_n_kernel(add_n_ptrs a, int k, long long n4, long long n, float* __restrict__ out) {
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long long i = t0; i < n4; i += stride) {
+    float4 s = *reinterpret_cast<const float4*>(a.p[0] + i * 4);
+#pragma unroll
+    for (int j = 1; j < 8; ++j) {      // (unrolled over the constant bound: the pointers stay in scalar registers; k is uniform)
+      if (j < k) {
+        const float4 v = *reinterpret_cast<const float4*>(a.p[j] + i * 4);
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+      }
+    }
+    *reinterpret_cast<float4*>(out + i * 4) = s;
+  }
+  for (long long i = n4 * 4 + t0; i < n; i += stride) {
+    float s = a.p[0][i];
+#pragma unroll
+    for (int j = 1; j < 8; ++j)
+      if (j < k) s += a.p[j][i];
+    out[i] = s;
+  }
+}
+
+extern "C" int tpgsr_add_n(const float* a0, const float* a1, const float* a2, const float* a3, const float* a4, const float* a5,
+                           const float* a6, const float* a7, int k, long long n, float* out, void* stream) {
+  const float* in[8] = {a0, a1, a2, a3, a4, a5, a6, a7};
+  TPGSR_CHECK_ARG(out && n > 0 && k >= 2 && k <= 8, "tpgsr_add_n: bad arguments (2 <= k <= 8 addends, n > 0)");
+  add_n_ptrs a;
+  bool vec = (((uintptr_t)out) & 15) == 0;
+  for (int j = 0; j < 8; ++j) {
+    TPGSR_CHECK_ARG(j >= k || in[j], "tpgsr_add_n: addend %d of %d is a null pointer", j, k);
+    a.p[j] = j < k ? in[j] : nullptr;
+    if (j < k) vec = vec && (((uintptr_t)in[j]) & 15) == 0;
+  }
+  const long long n4 = vec ? n / 4 : 0;
+  const long long work = n4 > (n - 4 * n4) ? n4 : n - 4 * n4;
+  int grid = (int)max((long long)1, min((long long)4096, (work + 255) / 256));
+  hipLaunchKernelGGL(add_n_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, k, n4, n, out);
+  TPGSR_LAUNCH_CHECK("tpgsr_add_n");
+}
+
 __global__ __launch_bounds__(256) void act_bwd_kernel(const float* x, const float* dy, long long n, int act, float* dx) {
   long long n4 = n >> 2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {

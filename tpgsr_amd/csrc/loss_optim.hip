@@ -283,6 +283,62 @@ extern "C" int tpgsr_image_loss_bwd(const float* out, const float* tgt, const fl
 }
 
 // ------------------------------------------------------------------------------------------------------
+// L1 loss (nn.L1Loss over all elements: the image criterion of `--arch rdn_tl`, interfaces/base.py:355-368)
+//   forward : partial[b][0] = sum |out - tgt| over workgroup b's elements, partial[b][1] = 0 -- the [nblk][2] rows of the image loss, so
+//             tpgsr_image_loss_finalize(partial, nblk, numel, 0, w, 0, loss) finishes it: loss = w * sum / numel (fp64 over the rows)
+//   backward: dout = dloss * w / numel * sign(out - tgt), sign(0) = 0 (ATen's l1_loss backward)
+// 16-byte loads while both pointers are 16-byte aligned (n4 groups of four), the rest element by element.
+// ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void l1_loss_fwd_kernel(const float* __restrict__ out, const float* __restrict__ tgt, long long n4,
+                                                          long long n, float* __restrict__ partial) {
+  __shared__ float red[4];
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  float ab = 0.f;
+  for (long long i = t0; i < n4; i += stride) {
+    const float4 a = *reinterpret_cast<const float4*>(out + i * 4), b = *reinterpret_cast<const float4*>(tgt + i * 4);
+    ab += (fabsf(a.x - b.x) + fabsf(a.y - b.y)) + (fabsf(a.z - b.z) + fabsf(a.w - b.w));
+  }
+  for (long long i = n4 * 4 + t0; i < n; i += stride) ab += fabsf(out[i] - tgt[i]);
+  ab = wave_sum(ab);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ab;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 2] = (red[0] + red[1]) + (red[2] + red[3]);
+    partial[blockIdx.x * 2 + 1] = 0.f;
+  }
+}
+
+extern "C" int tpgsr_l1_loss_fwd(const float* out, const float* tgt, long long n, float* partial, int nblk, void* stream) {
+  TPGSR_CHECK_ARG(out && tgt && partial && nblk > 0 && n > 0, "tpgsr_l1_loss_fwd: bad arguments");
+  const bool vec = ((((uintptr_t)out) | ((uintptr_t)tgt)) & 15) == 0;
+  hipLaunchKernelGGL(l1_loss_fwd_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, out, tgt, vec ? n / 4 : 0, n, partial);
+  TPGSR_LAUNCH_CHECK("tpgsr_l1_loss_fwd");
+}
+
+__device__ __forceinline__ float sign0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+
+__global__ __launch_bounds__(256) void l1_loss_bwd_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
+                                                          const float* __restrict__ dloss, float c, long long n4, long long n,
+                                                          float* __restrict__ dout) {
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const float g = dloss[0] * c;
+  for (long long i = t0; i < n4; i += stride) {
+    const float4 a = *reinterpret_cast<const float4*>(out + i * 4), b = *reinterpret_cast<const float4*>(tgt + i * 4);
+    *reinterpret_cast<float4*>(dout + i * 4) = make_float4(g * sign0(a.x - b.x), g * sign0(a.y - b.y), g * sign0(a.z - b.z), g * sign0(a.w - b.w));
+  }
+  for (long long i = n4 * 4 + t0; i < n; i += stride) dout[i] = g * sign0(out[i] - tgt[i]);
+}
+
+extern "C" int tpgsr_l1_loss_bwd(const float* out, const float* tgt, const float* dloss, long long n, float w, float* dout, void* stream) {
+  TPGSR_CHECK_ARG(out && tgt && dloss && dout && n > 0, "tpgsr_l1_loss_bwd: bad arguments");
+  const bool vec = ((((uintptr_t)out) | ((uintptr_t)tgt) | ((uintptr_t)dout)) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0, work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
+  const int grid = (int)max((long long)1, min((long long)4096, (work + 255) / 256));
+  hipLaunchKernelGGL(l1_loss_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, tgt, dloss, w / (float)n, n4, n, dout);
+  TPGSR_LAUNCH_CHECK("tpgsr_l1_loss_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------------
 // optimiser: global L2 norm, clip coefficient, Adam
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ x, long long n, float* __restrict__ partial) {

@@ -64,7 +64,7 @@ const std::unordered_map<std::string, Entry>& registry() {
       TPGSR_REG(tpgsr_bn_bwd_finalize), TPGSR_REG(tpgsr_bn_bwd_apply), TPGSR_REG(tpgsr_affine_act),
       TPGSR_REG_S(tpgsr_affine_act_bnd, tpgsr_bn_derive), TPGSR_REG_S(tpgsr_affine_act_pool_bnd, tpgsr_bn_derive), TPGSR_REG_S(tpgsr_bn_bwd_apply_bnd, tpgsr_bn_derive),
       TPGSR_REG(tpgsr_affine_act_pool), TPGSR_REG(tpgsr_affine_act_pool_bwd), TPGSR_REG(tpgsr_prelu_fwd),
-      TPGSR_REG(tpgsr_prelu_bwd), TPGSR_REG(tpgsr_add), TPGSR_REG(tpgsr_act_bwd), TPGSR_REG(tpgsr_nchw_to_nhwc),
+      TPGSR_REG(tpgsr_prelu_bwd), TPGSR_REG(tpgsr_add), TPGSR_REG(tpgsr_add_n), TPGSR_REG(tpgsr_act_bwd), TPGSR_REG(tpgsr_nchw_to_nhwc),
       TPGSR_REG(tpgsr_nhwc_to_nchw), TPGSR_REG(tpgsr_reduce_partials), TPGSR_REG(tpgsr_bigru_fwd),
       TPGSR_REG(tpgsr_bigru_bwd), TPGSR_REG(tpgsr_bigru_bwd2), TPGSR_REG(tpgsr_bigru_fwd_u), TPGSR_REG(tpgsr_bigru_bwd_u), TPGSR_REG_S(tpgsr_bigru_proj_fwd, tpgsr_bigru_proj_args), TPGSR_REG_S(tpgsr_gru_wgrad, tpgsr_gru_wgrad_args), TPGSR_REG(tpgsr_tps_grid_fwd), TPGSR_REG(tpgsr_tps_grid_bwd),
       TPGSR_REG(tpgsr_grid_sample_fwd), TPGSR_REG(tpgsr_grid_sample_bwd), TPGSR_REG(tpgsr_strip_resample_fwd),
@@ -73,7 +73,7 @@ const std::unordered_map<std::string, Entry>& registry() {
       TPGSR_REG(tpgsr_lstm_rec_gemm), TPGSR_REG(tpgsr_lstm_step_fwd), TPGSR_REG(tpgsr_lstm_seq_fwd), TPGSR_REG(tpgsr_lstm_seq_fwdg), TPGSR_REG(tpgsr_lstm_seq_bwd), TPGSR_REG(tpgsr_lstm_step_bwd), TPGSR_REG(tpgsr_softmax_prior_fwd),
       TPGSR_REG(tpgsr_semantic_loss_finalize), TPGSR_REG(tpgsr_softmax_prior_bwd), TPGSR_REG(tpgsr_tail_shiftsum_tanh), TPGSR_REG(tpgsr_shiftsum_nhwc),
       TPGSR_REG(tpgsr_tail_bwd), TPGSR_REG(tpgsr_image_loss_fwd), TPGSR_REG(tpgsr_image_loss_finalize),
-      TPGSR_REG(tpgsr_image_loss_bwd), TPGSR_REG(tpgsr_sumsq_partial), TPGSR_REG(tpgsr_clip_coef),
+      TPGSR_REG(tpgsr_image_loss_bwd), TPGSR_REG(tpgsr_l1_loss_fwd), TPGSR_REG(tpgsr_l1_loss_bwd), TPGSR_REG(tpgsr_sumsq_partial), TPGSR_REG(tpgsr_clip_coef),
       TPGSR_REG(tpgsr_adam_step), TPGSR_REG(tpgsr_step_inc), TPGSR_REG(tpgsr_scale_),
       TPGSR_REG(tpgsr_im2col3x3_c1), TPGSR_REG(tpgsr_col2im3x3_c1), TPGSR_REG(tpgsr_pad_channels),
       TPGSR_REG(tpgsr_semantic_loss_fwd), TPGSR_REG(tpgsr_semantic_loss_bwd), TPGSR_REG(tpgsr_split_bf_program),

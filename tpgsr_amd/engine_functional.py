@@ -18,7 +18,10 @@ Two ways to run it:
   summed by tpgsr_add), so autograd never runs an ATen kernel of its own that a replay would miss -- tests/test_opt_recorded_gpu.py
   compares replays on fresh inputs with the operator-by-operator run.
 * operator by operator through autograd (the reference implementation of the above; gradients accumulated by autograd into the arena's
-  `.grad` views)."""
+  `.grad` views).
+
+`FunctionalSREngine` (below) is the same adapter on the SR-network side of the protocol, for the `_TL` baseline backbones of the cascade loop
+(`TPGSR_SR_RECORD=0` switches ITS recording off)."""
 import os
 from typing import Dict, Optional
 
@@ -165,3 +168,134 @@ class FunctionalEngine:
         self.arena.attach_grads()
         torch.autograd.backward(logits, dlogits.reshape(logits.shape))
         return x.grad if need_dgray else None
+
+
+class FunctionalSREngine(FunctionalEngine):
+    """The SR-network side of the engine protocol (`TSRNEngine`'s: forward_pre / forward / backward with cascade slots) for a backbone
+    written operator by operator: the `_TL` baselines of the reference's ABLATION_SET (`--arch srresnet_tl | rdn_tl | srcnn_tl | vdsr_tl`,
+    model/{srresnet,rdn,srcnn,vdsr}.py), which interfaces/super_resolution.py:295-424 trains through the same cascade loop as TSRN_TL.
+    `TPGSRTrainStep`, `FusedAdam`, `ArenaPool` and `TextSREvaluator` drive the module through this adapter; `module(x, prior)` under
+    autograd keeps working on its own.
+
+    RECORDED (default, `TPGSR_SR_RECORD=0` switches it off): one trace per (N, H, W, training, slot, policy) -- the slot keeps the saved
+    activations of each cascade stage apart: a shared SR net runs `stu_iter` forward passes before any backward pass.  A forward and a
+    backward pass are one replay each: parameter gradients go through `functional.GRAD_SINK` into the arena, weight gradients run on the
+    weight-gradient stream with one batched slab reduce, every multi-consumer tensor of the module's forward is a `functional.fork`.
+    Otherwise operator by operator through autograd: the reference implementation of the recorded mode."""
+    FUSED = False
+    role = "sr"
+
+    def __init__(self, module: torch.nn.Module):
+        super().__init__(module)
+        self.record = os.environ.get("TPGSR_SR_RECORD", "1") != "0"
+
+    # ---- recorded mode ------------------------------------------------------------------------------------------------------------
+    def sr_plans(self, shape, training: bool, slot: int = 0) -> dict:
+        key = (tuple(shape), bool(training), slot, K.POLICY)
+        pl = self._plans.get(key)
+        if pl is None:
+            pl = self._plans[key] = self._trace_sr(tuple(shape), training)
+        return pl
+
+    def _trace_sr(self, shape, training):
+        dev = self.device
+        N = shape[0]
+        lr = torch.empty(*shape, device=dev)
+        prior = torch.empty(N, 37, 1, 26, device=dev)
+        fwd = Plan("sr_tl_fwd")
+        out = dict(fwd=fwd, lr=lr, prior=prior)
+        with recording(fwd), K.conv_terms(K.terms_for("sr", "fwd")):
+            if training:
+                t = prior.requires_grad_(True)
+                with torch.enable_grad():
+                    y = self.module(lr, t)
+            else:
+                with torch.no_grad():
+                    y = self.module(lr, prior)
+        assert y.is_contiguous() and y.shape[0] == N
+        out["sr"] = y.detach()
+        if not training:
+            return out
+        bwd = Plan("sr_tl_bwd")
+        bwd.overlap = os.environ.get("TPGSR_OVERLAP_WGRAD", "1") != "0"
+        bwd.deferred = [] if os.environ.get("TPGSR_DEFER_REDUCE", "1") != "0" else None
+        dsr = torch.empty_like(out["sr"])
+        self.arena.attach_grads()
+        grads = {p.data_ptr(): p.grad for p in self.module.parameters() if p.requires_grad}
+        got = []
+        h = t.register_hook(lambda g_: got.append(g_))
+        prev, Fh.GRAD_SINK = Fh.GRAD_SINK, grads
+        try:
+            with recording(bwd), K.conv_terms(K.terms_for("sr", "bwd")):
+                torch.autograd.backward(y, dsr)
+                if bwd.deferred is not None:
+                    K.flush_wgrad_reduces()
+                K._REC.join()
+        finally:
+            Fh.GRAD_SINK = prev
+            h.remove()
+        t.grad = None
+        if not got or not got[0].is_contiguous():
+            raise RuntimeError(f"{type(self.module).__name__}: the traced backward pass produced no contiguous text-prior gradient")
+        out.update(bwd=bwd, dsr=dsr, dprior=got[0], graph=y)       # `graph` keeps the saved activations alive
+        return out
+
+    # ---- the engine protocol --------------------------------------------------------------------------------------------------------
+    def forward_pre(self, lr, training, slot: int = 0, defer_join: bool = False):
+        """engine protocol: the prior-independent prologue `TSRNEngine` runs next to the text-prior generator.  Nothing here is worth
+        splitting out (the first conv of these backbones is a fraction of a percent of the pass): a no-op"""
+        return None
+
+    def _check_mode(self, training):
+        if bool(self.module.training) != bool(training):
+            raise RuntimeError(f"{type(self.module).__name__}: forward(training={training}) on a module in "
+                               f"{'train' if self.module.training else 'eval'}() mode")
+
+    def forward(self, lr, training, prior=None, slot: int = 0, defer_join: bool = False, pre_done: bool = False) -> torch.Tensor:
+        """lr (N, C, H, W), prior (N, 37, 1, 26) or None (zeros) -> SR image (N, C, 2H, 2W)"""
+        self._check_mode(training)
+        self.bind(lr.device)
+        N = lr.shape[0]
+        if prior is not None and tuple(prior.shape) != (N, 37, 1, 26):
+            raise ValueError(f"{type(self.module).__name__}: the text prior is (N, 37, 1, 26), got {tuple(prior.shape)}")
+        if self.record:
+            pl = self.sr_plans(lr.shape, training, slot)
+            K.copy(lr.contiguous(), pl["lr"], lr.numel())
+            if prior is None:
+                K.zero(pl["prior"], pl["prior"].numel())
+            else:
+                K.copy(prior.contiguous(), pl["prior"], prior.numel())
+            pl["fwd"].run()
+            if training:
+                self._pending_batches += 1
+                self._saved[slot] = (N, pl)
+            res = torch.empty_like(pl["sr"])
+            K.copy(pl["sr"], res, res.numel())
+            return res
+        with K.conv_terms(K.terms_for("sr", "fwd")):
+            if not training:
+                with torch.no_grad():
+                    return self.module(lr, prior)
+            t = (prior if prior is not None else torch.zeros(N, 37, 1, 26, device=lr.device)).detach().requires_grad_(True)
+            with torch.enable_grad():
+                y = self.module(lr.detach(), t)
+        self._saved[slot] = (t, y)
+        return y.detach()
+
+    def backward(self, x_shape, sr, dsr, slot: int = 0, defer_join: bool = False) -> torch.Tensor:
+        """d loss / d SR image -> d loss / d prior (N, 37, 1, 26); parameter gradients are accumulated into the arena"""
+        if slot not in self._saved:
+            raise RuntimeError(f"{type(self.module).__name__}: backward without a training-mode forward in slot {slot}")
+        if self.record:
+            n, pl = self._saved.pop(slot)
+            assert n == x_shape[0]
+            self.arena.attach_grads()                       # (same addresses as at trace time: the arena does not move)
+            K.copy(dsr.contiguous(), pl["dsr"], pl["dsr"].numel())
+            pl["bwd"].run()
+            return pl["dprior"]        # the plan's buffer of this slot: valid until the slot's next backward pass
+        t, y = self._saved.pop(slot)
+        self.arena.attach_grads()
+        with K.conv_terms(K.terms_for("sr", "bwd")):
+            torch.autograd.backward(y, dsr.reshape(y.shape))
+        return t.grad.contiguous()
+

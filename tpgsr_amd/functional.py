@@ -354,6 +354,10 @@ class _PReLU(torch.autograd.Function):
         dx = torch.empty_like(x)
         dap = torch.empty(nb, device=x.device)
         K.prelu_bwd(x, alpha, _c(dy), None, x.numel(), dx, dap, nb)
+        sa = _sink(alpha)
+        if sa is not None:
+            K.reduce_partials(dap, nb, 1, sa, accumulate=True)
+            return dx, None
         da = torch.empty(1, device=x.device)
         K.reduce_partials(dap, nb, 1, da, accumulate=False)
         return dx, da
@@ -383,26 +387,34 @@ def add(a, b):
 
 
 class _Fork(torch.autograd.Function):
-    """x -> (x, x) for a tensor with two consumers (the identity branch of a residual block): the two incoming gradients are summed by
-    tpgsr_add here, not by autograd's own accumulation (an ATen kernel -- and invisible to a recorded plan)"""
+    """x -> n views of x for a tensor with n consumers (the identity branch of a residual block, a text-prior map fed to every block):
+    the incoming gradients are summed here by ONE launch (tpgsr_add for two, tpgsr_add_n for up to eight, left to right in consumer
+    order), not by autograd's own accumulation (ATen kernels -- and invisible to a recorded plan)"""
 
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, n):
         _chk(x)
         ctx.set_materialize_grads(False)      # an unused consumer hands `None` to backward, not a zero tensor filled by an ATen kernel
-        return x.view_as(x), x.view_as(x)
+        return tuple(x.view_as(x) for _ in range(n))
 
     @staticmethod
-    def backward(ctx, ga, gb):
-        if ga is None or gb is None:
-            return ga if gb is None else gb
-        out = torch.empty_like(ga, memory_format=torch.contiguous_format)
-        K.add(_c(ga), _c(gb), ga.numel(), out)
-        return out
+    def backward(ctx, *gs):
+        live = [_c(g) for g in gs if g is not None]
+        if len(live) <= 1:
+            return (live[0] if live else None), None      # a single survivor is passed through: no launch
+        out = torch.empty_like(live[0], memory_format=torch.contiguous_format)
+        if len(live) == 2:
+            K.add(live[0], live[1], out.numel(), out)
+        else:
+            K.add_n(live, out.numel(), out)
+        return out, None
 
 
-def fork(x):
-    return _Fork.apply(x)
+def fork(x, n: int = 2):
+    """n views of x, one per consumer (2 <= n <= 8); their gradients are summed by one HIP launch in the backward pass"""
+    if not 2 <= n <= 8:
+        raise ValueError(f"fork: 2 to 8 consumers, got {n}")
+    return _Fork.apply(x, int(n))
 
 
 class _Cat(torch.autograd.Function):

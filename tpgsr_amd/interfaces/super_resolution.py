@@ -199,7 +199,7 @@ class TPGSRTrainStep:
     def __init__(self, sr_models, students, teacher, stu_iter=1, sr_share=True, tpg_share=False, gradient=True,
                  loss_weight=(1.0, 1e-4), lr=1e-3, betas=(0.5, 0.999), max_norm=0.25, process_group=None, world_size=1,
                  force_collectives=False, precision: Optional[str] = None, ssim_loss: bool = False, use_label: bool = False,
-                 use_distill: bool = True):
+                 use_distill: bool = True, image_crit: str = "image_loss"):
         # `--ssim_loss` (interfaces/super_resolution.py:388-391): every stage adds (1 - ssim(cascade_images, images_hr).mean()) * 10 to its image loss
         self.ssim_loss = bool(ssim_loss)
         # `--use_label` (:347-366): every stage adds mean(CTC(log_softmax(student logits), labels) * weighted_tics) -- step(..., labels=) then
@@ -211,6 +211,12 @@ class TPGSRTrainStep:
         # arithmetic policy of the step's GEMMs (kernels.py): `precision`, else an explicit TPGSR_CONV_PREC / set_conv_prec, else "x2" --
         # the benchmarked policy, gated at full size against the oracle on both north_star gates (tests/test_policy_x2*_gpu.py)
         self.precision = K.train_step_policy(precision)
+        # the image criterion (interfaces/base.py:355-368): "image_loss" = ImageLoss(gradient, loss_weight) of tsrn / tsrn_tl_cascade;
+        # "mse" = nn.MSELoss() of srresnet_tl / srcnn_tl / vdsr_tl (the image-loss kernels with the gradient term off and w0 = 1);
+        # "l1" = nn.L1Loss() of rdn_tl (tpgsr_l1_loss_fwd / _bwd).  All three: .mean() * 100, value computed on the teacher's stream
+        if image_crit not in ("image_loss", "mse", "l1"):
+            raise ValueError(f"TPGSRTrainStep: image_crit={image_crit!r}, expected 'image_loss', 'mse' or 'l1'")
+        self.image_crit = image_crit
         self.collective = world_size > 1 or bool(force_collectives)   # force: drive RCCL at world size 1 too (tests)
         _warn_hw_queues(self.collective)
         self.sr = list(sr_models) if isinstance(sr_models, (list, tuple)) else [sr_models]
@@ -220,6 +226,15 @@ class TPGSRTrainStep:
             teacher._engine().role = "teacher"      # arithmetic policy: its output is a soft target only (kernels.terms_for)
         self.stu_iter, self.sr_share, self.tpg_share = stu_iter, sr_share, tpg_share
         self.gradient, self.w0, self.w1 = bool(gradient), float(loss_weight[0]), float(loss_weight[1])
+        if image_crit != "image_loss":
+            self.gradient, self.w0, self.w1 = False, 1.0, 0.0
+        if self.collective:
+            from ..engine_functional import FunctionalSREngine
+            for m in self.sr:
+                if isinstance(m._engine(), FunctionalSREngine):
+                    raise NotImplementedError(f"TPGSRTrainStep: gradient exchange (world_size > 1 / force_collectives) with the operator-level SR "
+                                              f"backbone {type(m).__name__} is not supported: its engine has no gradient-bucket schedule "
+                                              "(DESIGN section 7).  Train the _TL baseline backbones on one GPU per process group of size 1.")
         mods = self.sr + self.stu
         # one flat parameter / gradient buffer: SR net(s) first, then the students = the order their gradients become final
         self.pool = ArenaPool(mods)
@@ -350,7 +365,10 @@ class TPGSRTrainStep:
                     K.ctc_loss(logits, 26 * 37, 37, ctc[0], ctc[1], ctc[2], None, N, 26, 37, 0, 0.0, st["ctc_nll"][i], None, False, ctc[4])
                     if not K.DRYRUN:
                         st["l_sem"][i].add_((st["ctc_nll"][i] * ctc[3]).mean())
-                K.image_loss_fwd(sr, hr, N, C, H2, W2, self.gradient, st["part_img"][i], _NBLK_IMG)
+                if self.image_crit == "l1":
+                    K.l1_loss_fwd(sr, hr, sr.numel(), st["part_img"][i], _NBLK_IMG)
+                else:
+                    K.image_loss_fwd(sr, hr, N, C, H2, W2, self.gradient, st["part_img"][i], _NBLK_IMG)
                 n_gp = N * min(C, 3) * H2 * W2 if self.gradient else 0
                 K.image_loss_finalize(st["part_img"][i], _NBLK_IMG, sr.numel(), n_gp, self.w0 * 100.0, self.w1 * 100.0, st["l_img"][i])
                 if self.ssim_loss:      # loss_img += (1 - ssim.mean()) * 10: the mean by tpgsr_ssim, the scalar arithmetic by three ATen launches
@@ -371,7 +389,10 @@ class TPGSRTrainStep:
         for i in range(self.stu_iter - 1, -1, -1):
             stu = self.stu[0 if self.tpg_share else i]
             srm = self.sr[0 if self.sr_share else i]
-            K.image_loss_bwd(srs[i], hr, st["dloss"], N, C, H2, W2, self.gradient, self.w0, self.w1, st["dsr"][i])
+            if self.image_crit == "l1":
+                K.l1_loss_bwd(srs[i], hr, st["dloss"], srs[i].numel(), self.w0, st["dsr"][i])
+            else:
+                K.image_loss_bwd(srs[i], hr, st["dloss"], N, C, H2, W2, self.gradient, self.w0, self.w1, st["dsr"][i])
             if self.ssim_loss:             # d/d sr of (1 - mean ssim) * 10, added to the first three channels of the image-loss gradient
                 K.ssim_bwd(srs[i], hr, st["ssim_win"], 11, N, C, H2, W2, st["ssim_gm"], None, -10.0 / (N * min(C, 3) * H2 * W2), st["dsr"][i], True)
             if i < self.stu_iter - 1:      # gradient arriving through the next stage's parse_crnn_data

@@ -1032,6 +1032,19 @@ def add(a, b, n, out):
     _launch("tpgsr_add", _p(a), _p(b), n, _p(out))
 
 
+def add_n(xs, n, out):
+    """out = ((xs[0] + xs[1]) + xs[2]) + ... in one launch, 2 <= len(xs) <= 8 (fixed left-to-right fp32 order: bitwise reproducible)"""
+    k = len(xs)
+    if not 2 <= k <= 8:
+        raise ValueError(f"add_n takes 2 to 8 addends, got {k}")
+    for t in xs:
+        if t.numel() != n:
+            raise ValueError(f"add_n: an addend has {t.numel()} elements, expected {n}")
+    if out.numel() != n:
+        raise ValueError(f"add_n: out has {out.numel()} elements, expected {n}")
+    _launch("tpgsr_add_n", *[_p(t) for t in xs], *([None] * (8 - k)), k, n, _p(out))
+
+
 def act_bwd(x, dy, n, act, dx):
     _launch("tpgsr_act_bwd", _p(x), _p(dy), n, act_code(act), _p(dx))
 
@@ -1313,6 +1326,22 @@ def image_loss_finalize(partial, nblk, n_mse, n_gp, w0, w1, loss):
 
 def image_loss_bwd(out, tgt, dloss, N, C_, H, W, gradient, w0, w1, dout):
     _launch("tpgsr_image_loss_bwd", _p(out), _p(tgt), _p(dloss), N, C_, H, W, int(gradient), w0, w1, _p(dout))
+
+
+def l1_loss_fwd(out, tgt, n, partial, nblk):
+    """partial [nblk][2] = {sum |out - tgt| per workgroup, 0}: image_loss_finalize(partial, nblk, n, 0, w, 0.0, loss) makes w * mean of it"""
+    if out.numel() != n or tgt.numel() != n:
+        raise ValueError(f"l1_loss_fwd: out / tgt have {out.numel()} / {tgt.numel()} elements, expected {n}")
+    if partial.numel() < 2 * nblk:
+        raise ValueError(f"l1_loss_fwd: partial holds {partial.numel()} floats, {nblk} workgroups write {2 * nblk}")
+    _launch("tpgsr_l1_loss_fwd", _p(out), _p(tgt), n, _p(partial), nblk)
+
+
+def l1_loss_bwd(out, tgt, dloss, n, w, dout):
+    """dout = dloss[0] * w / n * sign(out - tgt), sign(0) = 0"""
+    if out.numel() != n or tgt.numel() != n or dout.numel() != n:
+        raise ValueError(f"l1_loss_bwd: out / tgt / dout have {out.numel()} / {tgt.numel()} / {dout.numel()} elements, expected {n}")
+    _launch("tpgsr_l1_loss_bwd", _p(out), _p(tgt), _p(dloss), n, w, _p(dout))
 
 
 def sumsq_partial(x, n, partial, nblk):

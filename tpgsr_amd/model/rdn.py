@@ -6,8 +6,8 @@ import torch
 from torch import nn
 
 from .. import functional as Fh
-from .nn_params import Conv2dParams, _NoForward
-from .tl_common import InfoGen, spatial_text_embedding, zero_prior
+from .nn_params import Conv2dParams, EngineHolder, _NoForward
+from .tl_common import InfoGen, spatial_text_embedding, sr_engine, zero_prior
 
 
 class make_dense(nn.Module):
@@ -16,7 +16,8 @@ class make_dense(nn.Module):
         self.conv = Conv2dParams(nChannels, growthRate, kernel_size, padding=(kernel_size - 1) // 2, bias=False)
 
     def forward(self, x):
-        return Fh.cat([x, Fh.relu(self.conv(x))])
+        x, keep = Fh.fork(x)      # (conv and the concatenation: gradients summed by a HIP kernel, not by autograd)
+        return Fh.cat([keep, Fh.relu(self.conv(x))])
 
 
 class RDB_TL(nn.Module):
@@ -31,10 +32,10 @@ class RDB_TL(nn.Module):
         self.conv_1x1 = Conv2dParams(n + out_text_channels, nChannels, 1, padding=0, bias=False)
 
     def forward(self, x, text_emb):
-        out = x
+        out, skip = Fh.fork(x)
         for layer in self.dense_layers:
             out = layer(out)
-        return Fh.add(self.conv_1x1(Fh.cat([out, text_emb])), x)
+        return Fh.add(self.conv_1x1(Fh.cat([out, text_emb])), skip)
 
 
 class sub_pixel(nn.Module):
@@ -43,7 +44,7 @@ class sub_pixel(nn.Module):
         self.body = nn.Sequential(_NoForward())      # nn.PixelShuffle: fused into conv_up's store
 
 
-class RDN_TL(nn.Module):
+class RDN_TL(EngineHolder, nn.Module):
     def __init__(self, nChannel=4, nDenselayer=6, nFeat=64, scale_factor=2, growthRate=32, output_size=(32, 128), text_emb=37,
                  out_text_channels=32):
         super().__init__()
@@ -62,15 +63,21 @@ class RDN_TL(nn.Module):
         self.tps_outputsize = [16, 64]
         self.infoGen = InfoGen(text_emb, out_text_channels)
 
+    def _engine(self):
+        """engine adapter (tpgsr_amd/engine_functional.py FunctionalSREngine): lets TPGSRTrainStep / FusedAdam / ArenaPool / TextSREvaluator
+        drive this backbone as the SR network of the cascade loop (interfaces/super_resolution.py:295-424)"""
+        return sr_engine(self)
+
     def forward(self, x, text_emb=None):
         if text_emb is None:
             text_emb = zero_prior(x, self.infoGen.tconv1.in_channels)
         t = spatial_text_embedding(self.infoGen, text_emb, (x.shape[2], x.shape[3]))
-        F_ = self.conv1(Fh.to_nhwc(x))
+        t1, t2, t3 = Fh.fork(t, 3)      # every tensor with several consumers is forked: its gradients are summed by one HIP launch
+        F_, F_skip = Fh.fork(self.conv1(Fh.to_nhwc(x)))
         F_0 = self.conv2(F_)
-        F_1 = self.RDB1(F_0, t)
-        F_2 = self.RDB2(F_1, t)
-        F_3 = self.RDB3(F_2, t)
-        FGF = self.GFF_3x3(self.GFF_1x1(Fh.cat([F_1, F_2, F_3])))
-        us = self.conv_up(Fh.add(FGF, F_), out_ps=True)
+        F_1, F_1c = Fh.fork(self.RDB1(F_0, t1))
+        F_2, F_2c = Fh.fork(self.RDB2(F_1, t2))
+        F_3 = self.RDB3(F_2, t3)
+        FGF = self.GFF_3x3(self.GFF_1x1(Fh.cat([F_1c, F_2c, F_3])))
+        us = self.conv_up(Fh.add(FGF, F_skip), out_ps=True)
         return Fh.to_nchw(self.conv3(us))

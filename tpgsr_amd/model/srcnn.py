@@ -4,6 +4,8 @@ check the harness / fixtures / timer without a GPU, it is not part of the MI355X
 import torch
 from torch import nn
 
+from .nn_params import EngineHolder
+
 
 class SRCNN(nn.Module):
     def __init__(self, scale_factor=2, in_planes=3, STN=False, height=32, width=128):
@@ -23,7 +25,7 @@ class SRCNN(nn.Module):
         return self.conv3(self.relu2(self.conv2(self.relu1(self.conv1(x)))))
 
 
-class SRCNN_TL(nn.Module):
+class SRCNN_TL(EngineHolder, nn.Module):
     """`--arch srcnn_tl` (reference model/srcnn.py:50-106): SRCNN with the text-prior map concatenated in front of each conv.
     Unlike the CPU plumbing class above this one runs on the MI355X, operator by operator on the HIP kernels."""
 
@@ -44,6 +46,12 @@ class SRCNN_TL(nn.Module):
         self.stn = False
         self.infoGen = InfoGen(text_emb, out_text_channels)
 
+    def _engine(self):
+        """engine adapter (tpgsr_amd/engine_functional.py FunctionalSREngine): lets TPGSRTrainStep / FusedAdam / ArenaPool / TextSREvaluator
+        drive this backbone as the SR network of the cascade loop (interfaces/super_resolution.py:295-424)"""
+        from .tl_common import sr_engine
+        return sr_engine(self)
+
     def forward(self, x, text_emb=None):
         from .. import functional as Fh
         from .tl_common import spatial_text_embedding, zero_prior
@@ -51,6 +59,7 @@ class SRCNN_TL(nn.Module):
             text_emb = zero_prior(x, self.infoGen.tconv1.in_channels)
         h = Fh.upsample_nearest(Fh.to_nhwc(x), self.upscale_factor)
         t = spatial_text_embedding(self.infoGen, text_emb, (h.shape[1], h.shape[2]))
-        out = Fh.relu(self.conv1(Fh.cat([h, t])))
-        out = Fh.relu(self.conv2(Fh.cat([out, t])))
-        return Fh.to_nchw(self.conv3(Fh.cat([out, t])))
+        t1, t2, t3 = Fh.fork(t, 3)      # three consumers: their gradients are summed by one HIP launch, not by autograd
+        out = Fh.relu(self.conv1(Fh.cat([h, t1])))
+        out = Fh.relu(self.conv2(Fh.cat([out, t2])))
+        return Fh.to_nchw(self.conv3(Fh.cat([out, t3])))

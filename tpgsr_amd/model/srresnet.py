@@ -8,8 +8,8 @@ import torch
 from torch import nn
 
 from .. import functional as Fh
-from .nn_params import BatchNormParams, Conv2dParams, PReLUParams, _NoForward
-from .tl_common import InfoGen, spatial_text_embedding, zero_prior
+from .nn_params import BatchNormParams, Conv2dParams, EngineHolder, PReLUParams, _NoForward
+from .tl_common import InfoGen, spatial_text_embedding, sr_engine, zero_prior
 
 
 class ResidualBlock_TL(nn.Module):
@@ -23,9 +23,10 @@ class ResidualBlock_TL(nn.Module):
 
     def forward(self, x, text_emb):
         """NHWC in / out"""
+        x, skip = Fh.fork(x)      # two consumers (conv1 and the skip): their gradients are summed by a HIP kernel, not by autograd
         r = self.prelu(self.bn1(self.conv1(x)))
         r = self.bn2(self.conv2(Fh.cat([r, text_emb])))
-        return Fh.add(x, r)
+        return Fh.add(skip, r)
 
 
 class UpsampleBLock(nn.Module):
@@ -43,7 +44,7 @@ class UpsampleBLock(nn.Module):
         return self.prelu(self.conv(x, out_ps=True))
 
 
-class SRResNet_TL(nn.Module):
+class SRResNet_TL(EngineHolder, nn.Module):
     def __init__(self, scale_factor=2, STN=False, width=128, height=32, mask=False, text_emb=37, out_text_channels=32):
         super().__init__()
         self.emb_cls = text_emb
@@ -65,15 +66,20 @@ class SRResNet_TL(nn.Module):
         self.stn = False
         self.infoGen = InfoGen(text_emb, out_text_channels)
 
+    def _engine(self):
+        """engine adapter (tpgsr_amd/engine_functional.py FunctionalSREngine): lets TPGSRTrainStep / FusedAdam / ArenaPool / TextSREvaluator
+        drive this backbone as the SR network of the cascade loop (interfaces/super_resolution.py:295-424)"""
+        return sr_engine(self)
+
     def forward(self, x, text_emb=None):
         if text_emb is None:
             text_emb = zero_prior(x, self.emb_cls)
         t = spatial_text_embedding(self.infoGen, text_emb, (x.shape[2], x.shape[3]))
         h = Fh.to_nhwc(x)
-        b1 = self.block1[1](self.block1[0](h))
-        b = b1
+        ts = Fh.fork(t, 5)        # the text-prior map feeds all five residual blocks: one n-way gradient sum
+        b, b1 = Fh.fork(self.block1[1](self.block1[0](h)))
         for i in range(2, 7):
-            b = getattr(self, f"block{i}")(b, t)
+            b = getattr(self, f"block{i}")(b, ts[i - 2])
         b7 = self.block7[1](self.block7[0](b))
         out = Fh.add(b1, b7)
         for layer in self.block8:

@@ -38,5 +38,15 @@ def spatial_text_embedding(info_gen: InfoGen, text_emb: torch.Tensor, size):
     return Fh.interpolate_bilinear(info_gen.nhwc(Fh.to_nhwc(text_emb)), size)
 
 
+def sr_engine(module):
+    """the lazily built engine adapter of a `_TL` backbone (process-local state, like nn_params.EngineHolder's `_eng`)"""
+    eng = module.__dict__.get("_eng")
+    if eng is None:
+        from ..engine_functional import FunctionalSREngine
+        eng = FunctionalSREngine(module)
+        module.__dict__["_eng"] = eng
+    return eng
+
+
 def zero_prior(x, emb_cls):
     return torch.zeros(x.shape[0], emb_cls, 1, 26, device=x.device)

@@ -7,8 +7,8 @@ import torch
 from torch import nn
 
 from .. import functional as Fh
-from .nn_params import Conv2dParams
-from .tl_common import InfoGen, spatial_text_embedding, zero_prior
+from .nn_params import Conv2dParams, EngineHolder
+from .tl_common import InfoGen, spatial_text_embedding, sr_engine, zero_prior
 
 
 class Conv_ReLU_Block_TL(nn.Module):
@@ -19,10 +19,11 @@ class Conv_ReLU_Block_TL(nn.Module):
 
     def forward(self, x, text_emb):
         """NHWC in / out"""
-        return Fh.add(Fh.relu(self.conv(Fh.cat([x, text_emb]))), x)
+        x, skip = Fh.fork(x)      # (the block and its skip: gradients summed by a HIP kernel, not by autograd)
+        return Fh.add(Fh.relu(self.conv(Fh.cat([x, text_emb]))), skip)
 
 
-class VDSR_TL(nn.Module):
+class VDSR_TL(EngineHolder, nn.Module):
     def __init__(self, scale_factor=2, in_planes=4, width=32, height=128, STN=False, text_emb=37, out_text_channels=32):
         super().__init__()
         self.upscale_factor = scale_factor
@@ -42,12 +43,19 @@ class VDSR_TL(nn.Module):
         self.tps_outputsize = [height, width]
         self.stn = False        # the reference hard-codes it off (:169)
 
+    def _engine(self):
+        """engine adapter (tpgsr_amd/engine_functional.py FunctionalSREngine): lets TPGSRTrainStep / FusedAdam / ArenaPool / TextSREvaluator
+        drive this backbone as the SR network of the cascade loop (interfaces/super_resolution.py:295-424)"""
+        return sr_engine(self)
+
     def forward(self, x, text_emb=None):
         if text_emb is None:
             text_emb = zero_prior(x, self.infoGen.tconv1.in_channels)
         h = Fh.upsample_nearest(Fh.to_nhwc(x), self.upscale_factor)
         t = spatial_text_embedding(self.infoGen, text_emb, tuple(self.tps_outputsize))
+        ts = Fh.fork(t, 6)        # the text-prior map feeds all six blocks: one n-way gradient sum
+        h, h_skip = Fh.fork(h)
         out = Fh.relu(self.input(h))
         for i in range(1, 7):
-            out = getattr(self, f"block{i}")(out, t)
-        return Fh.to_nchw(Fh.add(self.output(out), h))
+            out = getattr(self, f"block{i}")(out, ts[i - 1])
+        return Fh.to_nchw(Fh.add(self.output(out), h_skip))
