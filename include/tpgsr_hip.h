@@ -32,7 +32,7 @@ extern "C" {
 
 const char* tpgsr_last_error(void);
 int tpgsr_version(void);
-/* sizeof of the argument structs (0 conv_args, 1 wgrad_args, 2 pack_desc, 3 wgrad_reduce_desc, 4 compose_bwd_desc, 5 split_desc, 6 image_desc, 7 gru_wgrad_args, 8 wgrad_batch_item, 9 bn_derive, 10 bigru_proj_args): a binding can verify its mirror */
+/* sizeof of the argument structs (0 conv_args, 1 wgrad_args, 2 pack_desc, 3 wgrad_reduce_desc, 4 compose_bwd_desc, 5 split_desc, 6 image_desc, 7 gru_wgrad_args, 8 wgrad_batch_item, 9 bigru_proj_args): a binding can verify its mirror */
 int tpgsr_sizeof(int which);
 
 /* ------------------------------------------------------------------------------------------------
@@ -100,34 +100,10 @@ typedef struct {
   int bnb_store_dz;       /* 1: `out` receives dz instead of da.  With bn_partial NULL this is a plain activation backward on the
                              way out -- out = da * act'(y * scale + shift), scale / shift optional (1 / 0) -- which is how the mish
                              in front of the tail convolution (model/tsrn.py:39,159) is differentiated without a launch of its own */
-  /* --- BatchNorm FINALIZE by the launch itself (fin_mode != 0; needs bn_partial).  What follows a statistics-producing convolution in
-   *     the reference -- nn.BatchNorm2d's batch mean / variance (forward) or batch_norm_backward's coefficients (backward) -- is a
-   *     reduction of bn_partial's ceil(M / 64) rows: a 3 us kernel behind a 5 us launch boundary, 36 times per C3 step.  With fin_mode
-   *     set tpgsr_conv_fwd guarantees it has run when the call's work is done: kernels that can (the whole-CU halo kernel) let their
-   *     LAST workgroup do it -- partial rows by write-through stores, one relaxed agent-scope ticket per workgroup, the last one reads
-   *     the rows back with L1-bypassing loads and sums them in a FIXED order, so the result does not depend on which workgroup it was --
-   *     for every other kernel the launcher appends tpgsr_bn_finalize / tpgsr_bn_bwd_finalize on the same stream.
-   *     mode 1 (forward):  scale / shift / save_mean / save_rstd (+ running statistics) as tpgsr_bn_finalize, count = M
-   *     mode 2 (backward): dgamma += sum dz xhat, dbeta += sum dz, coef [3][Cout] as tpgsr_bn_bwd_finalize (mean / rstd = bnb_mean / bnb_rstd) --- */
-  int fin_mode;
-  int fin_accumulate;        /* mode 2: 1 = add to dgamma / dbeta */
-  long long fin_count;       /* elements per channel the statistics were taken over */
-  int* fin_counter;          /* one zero-initialised int of device memory per BatchNorm layer; left at zero */
-  const float* fin_gamma;    /* [Cout] */
-  const float* fin_beta;     /* mode 1 */
-  const float* fin_bias;     /* mode 1: the convolution's bias when it is NOT part of `out` already (mean shift), or NULL */
-  float* fin_scale;          /* mode 1: [Cout] folded scale;    mode 2: coef [3][Cout] */
-  float* fin_shift;          /* mode 1: [Cout] folded shift;    mode 2: dgamma [Cout] or NULL */
-  float* fin_mean;           /* mode 1: save_mean [Cout] or NULL; mode 2: dbeta [Cout] or NULL */
-  float* fin_rstd;           /* mode 1: save_rstd [Cout] or NULL */
-  float* fin_rm;             /* mode 1: running_mean / running_var [Cout] or NULL */
-  float* fin_rv;
-  float fin_momentum;
-  float fin_eps;
   /* --- granularity of bn_partial (round 5).  0 / 1: one row per 64-pixel block (every kernel).  3: one row per THREE consecutive blocks
    *     = per 192-pixel super-tile of the whole-CU halo kernel, [ceil(ceil(M / 64) / 3)][2][Cout] -- a third of the rows for whoever
-   *     reduces them (csrc/bn_derive.h: every workgroup of the consuming launch).  Only the whole-CU kernel honours 3: ask
-   *     tpgsr_conv_bn_row_tiles() first, a launch that lands on any other kernel with 3 set is refused.  Not with fin_mode. --- */
+   *     reduces them (tpgsr_bn_finalize / tpgsr_bn_bwd_finalize).  Only the whole-CU kernel honours 3: ask tpgsr_conv_bn_row_tiles()
+   *     first, a launch that lands on any other kernel with 3 set is refused.  reserved1 keeps in2_scale 8-byte aligned. --- */
   int bn_row_tiles;
   int reserved1;
   /* --- scaled residual operand (round 6): a = in * in_scale[c] + in_shift[c] + in2 * in2_scale[c].  What it is for: the apply pass of
@@ -380,49 +356,6 @@ int tpgsr_bn_bwd_finalize(const float* partial, int nblk, int C, long long count
 /* pass 2: dy = coef0*dz + coef1*y + coef2 (dz recomputed from da(+da2), y) */
 int tpgsr_bn_bwd_apply(const float* da, const float* da2, const float* y, long long M, int C, const float* scale,
                        const float* shift, int act, const float* coef, float* dy, void* stream);
-/* ------------------------------------------------------------------------------------------------
- * BatchNorm finalize inside the launch that consumes it (round 5; csrc/bn_derive.h).  The reduction of the producing convolution's
- * partial rows that nn.BatchNorm2d's batch statistics (model/tsrn.py:376,380; model/stn_head.py:15; forward) and batch_norm_backward's
- * coefficients (backward) need is done by the FIRST CONSUMER's launch instead of a launch of its own: the first ceil(C / 16) workgroups
- * of its grid each sum the rows of 16 channels (fp64, fixed order), publish by write-through stores and arrive on `flag`; every workgroup
- * waits for the flag (its first loads already in flight) and reads the published values with L1-bypassing loads.  A wait that never ends
- * poisons the outputs with NaN.  tpgsr_bn_finalize / tpgsr_bn_bwd_finalize stay for consumers without the prologue.
- * C: 8, or a multiple of 16 up to 512; the grid must have at least ceil(C / 16) workgroups (M C >= 1024 ceil(C / 16)).
- *   forward  (tpgsr_affine_act_bnd, tpgsr_affine_act_pool_bnd): reads rows / count / bias / gamma / beta, writes scale / shift
- *            (+ save_mean / save_rstd / running statistics when set) exactly as tpgsr_bn_finalize does
- *   backward (tpgsr_bn_bwd_apply_bnd): reads rows ([.][0][c] = sum dz, [.][1][c] = sum dz * xhat) / count / gamma / save_mean /
- *            save_rstd, writes coef and dgamma / dbeta (+= when accumulate) exactly as tpgsr_bn_bwd_finalize does
- * ---------------------------------------------------------------------------------------------- */
-typedef struct tpgsr_bn_derive {
-  const float* rows;      /* [nrows][2][C] */
-  int nrows, C;
-  long long count;        /* elements per channel the rows were summed over */
-  const float* bias;      /* forward: the convolution's bias when it is not part of the stored map (shifts the mean only) or NULL */
-  const float* gamma;     /* [C] */
-  const float* beta;      /* forward */
-  float* running_mean;    /* forward, optional: updated with `momentum` (unbiased variance) */
-  float* running_var;
-  float momentum, eps;
-  float* scale;           /* forward out: folded scale / shift [C] */
-  float* shift;
-  float* save_mean;       /* forward: out (optional); backward: in */
-  float* save_rstd;
-  float* dgamma;          /* backward, optional */
-  float* dbeta;
-  float* coef;            /* backward, optional out [3][C] */
-  int accumulate;         /* backward: 1 = add to dgamma / dbeta */
-  int reserved;
-  unsigned* flag;         /* one word of device memory, ZERO when the launch starts (tpgsr_zero earlier on the stream): the arrival counter
-                             of the launch's deriver workgroups; the launch leaves ceil(C / 16) in it */
-} tpgsr_bn_derive;
-/* tpgsr_affine_act with the BatchNorm finalized in the launch: out = act(scale[c] * x + shift[c]) */
-int tpgsr_affine_act_bnd(const tpgsr_bn_derive* d, const float* x, long long M, int act, float* out, void* stream);
-/* tpgsr_affine_act_pool likewise (STN head: conv -> BN -> ReLU -> max-pool, model/stn_head.py:34-45) */
-int tpgsr_affine_act_pool_bnd(const tpgsr_bn_derive* d, const float* x, int N, int H, int W, int act, int pool_h, int pool_w,
-                              float* out, void* stream);
-/* tpgsr_bn_bwd_finalize + tpgsr_bn_bwd_apply in one launch: dy = coef0 * dz + coef1 * y + coef2, dz = (da + da2) * act'(scale * y + shift) */
-int tpgsr_bn_bwd_apply_bnd(const tpgsr_bn_derive* d, const float* da, const float* da2, const float* y, long long M,
-                           const float* scale, const float* shift, int act, float* dy, void* stream);
 
 /* out = act(scale[c]*x + shift[c]) over an [M][C] tensor (scale/shift optional, C % 4 == 0): materialises an activation
  * once where re-applying it per filter tap in the consumer's loader would cost more (mish before a 3x3 / 9x1 conv). */

@@ -49,7 +49,7 @@ def test_struct_layouts(lib):
     lib.tpgsr_sizeof.restype = ctypes.c_int
     for which, st in enumerate(_lib.ABI_STRUCTS):
         assert lib.tpgsr_sizeof(which) == ctypes.sizeof(st), st.__name__
-    assert len(_lib.ABI_STRUCTS) == 11 and lib.tpgsr_sizeof(len(_lib.ABI_STRUCTS)) == -1    # the list covers every struct the library knows
+    assert len(_lib.ABI_STRUCTS) == 10 and lib.tpgsr_sizeof(len(_lib.ABI_STRUCTS)) == -1    # the list covers every struct the library knows
 
 
 def test_error_reporting_without_gpu(lib):

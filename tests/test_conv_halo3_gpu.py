@@ -1,7 +1,8 @@
 """GPU: the whole-CU halo kernel (csrc/conv_halo3.hip: one workgroup per CU on three 64-pixel tiles at once; the SR trunk's 3x3 convolutions,
 model/tsrn.py:375-379) against the two-workgroup halo kernel it replaces -- same arithmetic, same summation order per output, so BITWISE the
 same outputs and BatchNorm statistics -- and against fp64, over shapes whose 192-pixel super-tiles span rows and images, ragged ends,
-every fused prologue, the BatchNorm-backward epilogue, multiple rounds per workgroup and multiple column tiles."""
+every fused prologue, the BatchNorm-backward epilogue, multiple rounds per workgroup and multiple column tiles; and its coarser statistics
+rows (tpgsr_conv_args.bn_row_tiles = 3) against the per-64-pixel rows."""
 import math
 
 import pytest
@@ -176,3 +177,58 @@ def test_scaled_residual_loader_is_the_batchnorm_backward_apply(N, H, W, terms):
     # the two forms round dy differently (fma chain in the loader vs the apply kernel) before the same split: a few bf16-term ulps
     tol = 2e-2 if terms == 1 else 2e-4
     assert e < tol and ep < 10 * tol and not torch.isnan(o1).any()
+
+
+@pytest.mark.parametrize("shape", [(48, 16, 64, 64, 64), (37, 16, 64, 64, 64), (48, 8, 25, 128, 256)])      # (37: 592 tiles = 197 super-tiles + 1 tile)
+def test_coarse_statistics_rows_of_the_whole_cu_kernel(shape):
+    """bn_row_tiles = 3: one row per 192-pixel super-tile == the three per-64-pixel rows added in tile order, bit for bit; forward
+    statistics and the BatchNorm-backward sums alike; a kernel that cannot honour it refuses the launch"""
+    from tpgsr_amd import _lib, kernels as K
+    from tpgsr_amd._lib import TpgsrKernelError
+    lib = _lib.load()
+    N, H, W, Ci, Co = shape
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(N * H * W, Ci, generator=g).to(DEV)
+    w = (torch.randn(9 * Ci, Co, generator=g) / math.sqrt(9 * Ci)).to(DEV)
+    geom = K.ConvGeom(N, H, W, Ci, Co, 3, 3, 1, 1)
+    M, nblk = geom.M, (geom.M + 63) // 64
+    with K.conv_terms(2):
+        K.make_bf_twin(w, Ci)
+        fine, out0 = torch.full((nblk, 2, Co), float("nan"), device=DEV), torch.empty(M, Co, device=DEV)
+        K.conv_fwd(K.make_conv_args(geom, x, w, out0, bn_partial=fine))
+        a = K.make_conv_args(geom, x, w, torch.empty(M, Co, device=DEV), bn_partial=torch.full((nblk, 2, Co), float("nan"), device=DEV), bn_coarse=True)
+        assert a.bn_row_tiles == 3, "this shape is the whole-CU kernel's"
+        nr = K.bn_rows(M, 3)
+        coarse = torch.full((nr, 2, Co), float("nan"), device=DEV)
+        out1 = torch.empty(M, Co, device=DEV)
+        a = K.make_conv_args(geom, x, w, out1, bn_partial=coarse, bn_coarse=True)
+        K.conv_fwd(a)
+        torch.cuda.synchronize()
+        assert torch.equal(out0, out1)
+        pad = torch.zeros(nr * 3, 2, Co, device=DEV)
+        pad[:nblk] = fine
+        p3 = pad.view(nr, 3, 2, Co)
+        assert torch.equal(coarse, (p3[:, 0] + p3[:, 1]) + p3[:, 2])
+        # backward sums through the same flush
+        y, mean, rstd = torch.randn(M, Co, generator=g).to(DEV), torch.randn(Co, generator=g).to(DEV), (torch.rand(Co, generator=g) + 0.5).to(DEV)
+        sc, sh = torch.rand(Co, generator=g).to(DEV) + 0.5, torch.randn(Co, generator=g).to(DEV)
+        res = []
+        for coarse_on in (False, True):
+            part = torch.full((nr if coarse_on else nblk, 2, Co), float("nan"), device=DEV)
+            bnb = dict(y=y, mean=mean, rstd=rstd, scale=sc, shift=sh, act="mish", partial=part, coarse=coarse_on)
+            K.conv_fwd(K.make_conv_args(geom, x, w, torch.empty(M, Co, device=DEV), bnb=bnb))
+            assert bnb["row_tiles"] == (3 if coarse_on else 1)
+            res.append(part)
+        torch.cuda.synchronize()
+        pad[:] = 0
+        pad[:nblk] = res[0]
+        p3 = pad.view(nr, 3, 2, Co)
+        assert torch.equal(res[1], (p3[:, 0] + p3[:, 1]) + p3[:, 2])
+        # the two-workgroup kernel cannot: loud refusal, not silently finer rows
+        lib.tpgsr_halo3_set_enabled(0)
+        try:
+            assert lib.tpgsr_conv_bn_row_tiles(__import__("ctypes").byref(a)) == 1
+            with pytest.raises(TpgsrKernelError, match="bn_row_tiles"):
+                K.conv_fwd(a)
+        finally:
+            lib.tpgsr_halo3_set_enabled(1)

@@ -108,8 +108,11 @@ def test_hd64_plans_have_no_fused_32_unit_kernels(sig64):
 
 @pytest.mark.timeout(600)
 def test_default_plans_equal_parent_launch_for_launch():
-    """hidden_units = 32: kernel names, stream ids, launch geometry and order are those recorded on the commit before the 64-unit scans
-    (tests/golden/plan_signature_hd32.json, written once by this file's SIGNATURE script on that commit)"""
+    """hidden_units = 32: kernel names, stream ids, launch geometry and order are those of commit b494a6b, the last one whose
+    tpgsr_conv_args carried the 15 fin_* fields of the retired last-workgroup BatchNorm finalize.  The CRCs cover field names, so
+    tests/golden/plan_signature_hd32.json is this file's SIGNATURE script run on the tree without those fields; run on b494a6b with
+    fields() skipping exactly those names it gives the same 314 + 186 lines, line for line.  b494a6b's own golden in turn pinned the
+    commit before the 64-unit scans."""
     want = json.load(open(os.path.join(GOLD, "plan_signature_hd32.json")))
     got = _signature(32)
     for tag in ("tl", "plain"):

@@ -32,10 +32,7 @@ class ConvArgs(C.Structure):
                 ("in_b", vp), ("cin_a", ci), ("in_b_ld", ci), ("in_dil_w", ci), ("wt_ld", ci), ("wt_coff", ci), ("stride_w", ci),
                 ("terms", ci), ("kp", ci), ("wt_bf", vp), ("wt_bf_cin", ci), ("reserved0", ci),
                 ("bnb_y", vp), ("bnb_mean", vp), ("bnb_rstd", vp), ("bnb_scale", vp), ("bnb_shift", vp), ("bnb_act", ci), ("bnb_store_dz", ci),
-                ("fin_mode", ci), ("fin_accumulate", ci), ("fin_count", ll), ("fin_counter", vp), ("fin_gamma", vp), ("fin_beta", vp),
-                ("fin_bias", vp), ("fin_scale", vp), ("fin_shift", vp), ("fin_mean", vp), ("fin_rstd", vp), ("fin_rm", vp), ("fin_rv", vp),
-                ("fin_momentum", cf), ("fin_eps", cf), ("bn_row_tiles", ci), ("reserved1", ci), ("in2_scale", vp),
-                ("sk_part", vp), ("sk_splits", ci), ("reserved2", ci)]
+                ("bn_row_tiles", ci), ("reserved1", ci), ("in2_scale", vp), ("sk_part", vp), ("sk_splits", ci), ("reserved2", ci)]
 
 
 class WgradArgs(C.Structure):
@@ -81,13 +78,6 @@ class ImageDesc(C.Structure):
     _fields_ = [("offset", ll), ("H", ci), ("W", ci), ("xb_off", ci), ("xk_off", ci), ("kx", ci), ("yb_off", ci), ("yk_off", ci), ("ky", ci)]
 
 
-class BnDerive(C.Structure):
-    """tpgsr_bn_derive: a BatchNorm finalized inside its first consumer's launch (csrc/bn_derive.h)"""
-    _fields_ = [("rows", vp), ("nrows", ci), ("C", ci), ("count", ll), ("bias", vp), ("gamma", vp), ("beta", vp),
-                ("running_mean", vp), ("running_var", vp), ("momentum", cf), ("eps", cf), ("scale", vp), ("shift", vp),
-                ("save_mean", vp), ("save_rstd", vp), ("dgamma", vp), ("dbeta", vp), ("coef", vp), ("accumulate", ci), ("reserved", ci), ("flag", vp)]
-
-
 class PlanArg(C.Union):
     """tpgsr_plan_arg: one launch argument of a native plan (pointer / integer / float)"""
     _fields_ = [("p", vp), ("i", ll), ("f", C.c_double)]
@@ -123,9 +113,6 @@ _SIGS = {
     "tpgsr_bigru_proj_supported": (ci, [C.POINTER(BigruProjArgs)]),
     "tpgsr_bigru_proj_fwd": (ci, [C.POINTER(BigruProjArgs), vp]),
     "tpgsr_bigru_proj_set_enabled": (None, [ci]),
-    "tpgsr_affine_act_bnd": (ci, [C.POINTER(BnDerive), vp, ll, ci, vp, vp]),
-    "tpgsr_affine_act_pool_bnd": (ci, [C.POINTER(BnDerive), vp, ci, ci, ci, ci, ci, ci, vp, vp]),
-    "tpgsr_bn_bwd_apply_bnd": (ci, [C.POINTER(BnDerive), vp, vp, vp, ll, vp, vp, ci, vp, vp]),
     "tpgsr_wgrad_splits": (ci, [ci, ci, ci]),
     "tpgsr_conv_wgrad": (ci, [C.POINTER(WgradArgs), vp]),
     "tpgsr_wgrad_halo_plan": (ci, [C.POINTER(ConvArgs), C.POINTER(ci), C.POINTER(C.c_longlong)]),
@@ -253,8 +240,7 @@ _SIGS = {
 EXPORTED_SYMBOLS = sorted(list(_SIGS.keys()) + ["tpgsr_last_error"])
 
 # the argument structs of the C ABI, in tpgsr_sizeof(which) order (csrc/error.cpp)
-ABI_STRUCTS = (ConvArgs, WgradArgs, PackDesc, WgradReduceDesc, ComposeBwdDesc, SplitDesc, ImageDesc, GruWgradArgs, WgradBatchItem, BnDerive,
-               BigruProjArgs)
+ABI_STRUCTS = (ConvArgs, WgradArgs, PackDesc, WgradReduceDesc, ComposeBwdDesc, SplitDesc, ImageDesc, GruWgradArgs, WgradBatchItem, BigruProjArgs)
 
 _lib = None
 

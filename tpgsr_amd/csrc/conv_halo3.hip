@@ -159,7 +159,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_xbf_kernel(tpgsr_conv_args 
       if (!item(PN{}, P0{})) break;
     }
     __syncthreads();        // the final barrier (the consumers' last statistics flush)
-    goto fin_tail;
+    return;
   }
 
   {
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_xbf_kernel(tpgsr_conv_args 
 #pragma unroll
         for (int m = 0; m < H3_TM; ++m)
           if ((pend_mblk + m) * 64 < M)
-            xbf_bn_flush<1, 1>(a, M, pend_n0, pend_mblk + m, tid, red_base + (((ndone - 1) & 1) * H3_TM + m) * 256, a.fin_mode != 0);
+            xbf_bn_flush<1, 1>(a, M, pend_n0, pend_mblk + m, tid, red_base + (((ndone - 1) & 1) * H3_TM + m) * 256);
       }
       pend_mblk = -1;
     }
@@ -538,20 +538,6 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_xbf_kernel(tpgsr_conv_args 
   __syncthreads();            // the final barrier
   flush_pending();
   }
-fin_tail:
-  // BatchNorm finalize by the LAST workgroup (tpgsr_conv_args.fin_mode): this workgroup's partial rows have left as write-through
-  // stores; once they are acknowledged it draws a ticket, and whoever draws the last one reduces all rows (conv_xbf_common.h)
-  if (a.fin_mode) {
-    __shared__ int s_ticket;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) s_ticket = __hip_atomic_fetch_add(a.fin_counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (s_ticket == (int)gridDim.x - 1) {
-      xbf_fin_last(a, M, tid, 512, reinterpret_cast<double*>(hsm));
-      if (tid == 0) __hip_atomic_store(a.fin_counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
 }
 
 /* upper bound of the halo length of any run of 64 * H3_TM consecutive output pixels (cf. halo_capacity in conv_xbf.hip) */
@@ -561,8 +547,6 @@ static int halo3_capacity(const tpgsr_conv_args* a) {
   const int img_wraps = (ohw % P == 0) ? 0 : (P - 1) / ohw + 1;
   return P - 1 + row_wraps * (a->KW - 1) + img_wraps * (a->KH - 1) * Wp + (a->KH - 1) * Wp + a->KW;
 }
-
-extern "C" void tpgsr_conv_fin_fused_mark(void);      // conv_mfma.hip
 
 extern "C" int tpgsr_halo3_trace(unsigned long long* buf) {   // buf: 8 * 8 * 256 uint64 of device memory, or nullptr to switch off
   if (hipMemcpyToSymbol(HIP_SYMBOL(g_halo3_trace), &buf, sizeof(buf)) != hipSuccess) {
@@ -609,13 +593,13 @@ extern "C" int tpgsr_conv_halo3_would_take(const tpgsr_conv_args* a, long long M
 
 /* 1 when a launch with a scaled residual operand (tpgsr_conv_args.in2_scale) is this kernel's -- the only one whose loader has it */
 extern "C" int tpgsr_conv_in2_scale_ok(const tpgsr_conv_args* a) {
-  if (!a || !(a->terms > 0 && a->wt_bf && (a->Cin & 3) == 0 && (a->wt_coff & 31) == 0) || a->fin_mode || !a->in2 || !a->in_scale || a->in_act || a->in_b) return 0;
+  if (!a || !(a->terms > 0 && a->wt_bf && (a->Cin & 3) == 0 && (a->wt_coff & 31) == 0) || !a->in2 || !a->in_scale || a->in_act || a->in_b) return 0;
   return halo3_takes(a, (long long)a->N * a->OH * a->OW, 37) > 0 ? 1 : 0;
 }
 
 /* tpgsr_conv_args.bn_row_tiles: 3 when tpgsr_conv_fwd(a) lands here (the dispatch of conv_mfma.hip / conv_xbf.hip up to this kernel) */
 extern "C" int tpgsr_conv_bn_row_tiles(const tpgsr_conv_args* a) {
-  if (!a || !(a->terms > 0 && a->wt_bf && (a->Cin & 3) == 0 && (a->wt_coff & 31) == 0) || a->fin_mode) return 1;
+  if (!a || !(a->terms > 0 && a->wt_bf && (a->Cin & 3) == 0 && (a->wt_coff & 31) == 0)) return 1;
   const int ld = (a->in_scale ? 1 : 0) | (a->in_act ? 2 : 0) | (a->in2 ? 4 : 0) | (a->in_ps ? 8 : 0) | (a->in_b ? 16 : 0);
   return halo3_takes(a, (long long)a->N * a->OH * a->OW, ld) > 0 ? H3_TM : 1;
 }
@@ -625,8 +609,8 @@ extern "C" int tpgsr_conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M
   const int T = a->terms;
   const int Lcap = halo3_takes(a, M, ld);
   if (Lcap <= 0) return 0;
-  TPGSR_CHECK_ARG(a->bn_row_tiles == 0 || a->bn_row_tiles == 1 || (a->bn_row_tiles == H3_TM && !a->fin_mode),
-                  "tpgsr_conv_fwd(halo3): bn_row_tiles %d (0, 1 or %d without fin_mode)", a->bn_row_tiles, H3_TM);
+  TPGSR_CHECK_ARG(a->bn_row_tiles == 0 || a->bn_row_tiles == 1 || a->bn_row_tiles == H3_TM,
+                  "tpgsr_conv_fwd(halo3): bn_row_tiles %d (0, 1 or %d)", a->bn_row_tiles, H3_TM);
   const size_t lds = (size_t)2 * T * H3_PLANE + 2 * H3_TM * 1024 + 8 * 4096;
   const long long nst = (long long)cdiv(cdiv(M, 64), H3_TM) * cdiv(a->Cout, 64);
   const void* fn = nullptr;
@@ -669,6 +653,5 @@ extern "C" int tpgsr_conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M
     tpgsr_set_error("tpgsr_conv_fwd(halo3): launch failed: %s", hipGetErrorString(hipGetLastError()));
     return TPGSR_ERR_LAUNCH;
   }
-  if (a->fin_mode) tpgsr_conv_fin_fused_mark();      // this kernel's last workgroup finalizes the BatchNorm (conv_mfma.hip: no extra launch)
   return 1;
 }

@@ -292,9 +292,6 @@ class BNLayer:
         self.pad_to = max(C_, pad_to)
         eng._bn_layers.append(self)
         self.scale = self.shift = self.save_mean = self.save_rstd = self.coef = None   # bound per plan by use(ws)
-        # ticket counters of the convolution launches that finalize this BatchNorm themselves (forward / backward; left at zero by the
-        # last workgroup; launches sharing one never overlap: they are the same layer's, in stream order)
-        self.tickets = torch.zeros(2, dtype=torch.int32, device=eng.device)
 
     def use(self, ws):
         """Batch statistics / folded scale+shift belong to ONE forward: they live in the plan's workspace (a network
@@ -322,25 +319,6 @@ class BNLayer:
             K.bn_finalize(None, 0, self.C, 0, None, self.gamma, self.beta, self.rm, self.rv, self.scale, self.shift,
                           eval_mode=True)
 
-    def derive_fwd(self, M, conv_bias, row_tiles=1):
-        """descriptor (kernels.make_bn_derive) for the FIRST consumer of this training-mode BatchNorm's output: that launch reduces the
-        producing convolution's partial rows itself (csrc/bn_derive.h) and finalize() is NOT recorded; None when the channel count is
-        outside the prologue's range or the switch is off (then: finalize() + the plain consumer)"""
-        if not K.bn_derive_ok(self.C, M):
-            return None
-        part, _ = self.partial(M)
-        return K.make_bn_derive(part, K.bn_rows(M, row_tiles), self.C, M, self.gamma, bias=conv_bias, beta=self.beta, running_mean=self.rm,
-                                running_var=self.rv, scale=self.scale, shift=self.shift, save_mean=self.save_mean,
-                                save_rstd=self.save_rstd)
-
-    def fin(self, M, conv_bias):
-        """kwargs (`bn_fin=`) for the training-mode convolution that leaves this BatchNorm's statistics in partial(M): the launch
-        finalizes them itself (then finalize() is NOT recorded), or None when that is switched off / the fp32 kernels run"""
-        if not K.bn_fin_fused():
-            return None
-        return dict(mode=1, count=M, counter=self.tickets[0:1], gamma=self.gamma, beta=self.beta, bias=conv_bias, scale=self.scale,
-                    shift=self.shift, save_mean=self.save_mean, save_rstd=self.save_rstd, running_mean=self.rm, running_var=self.rv)
-
     @property
     def loader(self):
         return dict(in_scale=self.scale, in_shift=self.shift)
@@ -353,12 +331,8 @@ class BNLayer:
             return None
         nblk = (M + 63) // 64
         part = self.eng.scratch("bnb_partial" + K.stream_tag(), nblk * 2 * self.C)
-        d = dict(y=y, mean=self.save_mean, rstd=self.save_rstd, scale=self.scale, shift=self.shift, act=act, partial=part,
-                 coarse=not K.bn_fin_fused())      # (make_conv_args writes the granularity it settled on back as d["row_tiles"])
-        if K.bn_fin_fused():       # the producing launch also reduces the sums (backward(..., fused=) then records the apply only)
-            d["fin"] = dict(mode=2, count=M, counter=self.tickets[1:2], gamma=self.gamma, coef=self.coef,
-                            dgamma=self.eng.G[self.prefix + ".weight"], dbeta=self.eng.G[self.prefix + ".bias"], accumulate=True)
-        return d
+        return dict(y=y, mean=self.save_mean, rstd=self.save_rstd, scale=self.scale, shift=self.shift, act=act, partial=part,
+                    coarse=True)      # (make_conv_args writes the granularity it settled on back as d["row_tiles"])
 
     def backward(self, da, da2, y, M, act, dy, fused=None):
         """dy = dL/d(pre-BN y) from da (+da2) = dL/d act(BN(y)); accumulates dgamma/dbeta into the arena.
@@ -367,18 +341,10 @@ class BNLayer:
         if fused is not None:
             assert da2 is None and fused["y"] is y and fused["act"] == act
             nblk, part = K.bn_rows(M, fused.get("row_tiles", 1)), fused["partial"]
-            if fused.get("fin") is not None and K.BN_FIN_FUSE:      # finalized by the producing launch
-                K.bn_bwd_apply(da, da2, y, M, self.C, self.scale, self.shift, act, self.coef, dy)
-                return
         else:
             nblk = min(1024, max(1, M // 64))
             part = eng.scratch("bnb_partial" + K.stream_tag(), nblk * 2 * self.C)
             K.bn_bwd_reduce(da, da2, y, M, self.C, self.scale, self.shift, self.save_mean, self.save_rstd, act, part, nblk)
-        if K.bn_derive_ok(self.C, M):      # coefficients + dgamma / dbeta derived by the apply launch itself: one launch instead of two
-            d = K.make_bn_derive(part, nblk, self.C, M, self.gamma, save_mean=self.save_mean, save_rstd=self.save_rstd,
-                                 dgamma=eng.G[self.prefix + ".weight"], dbeta=eng.G[self.prefix + ".bias"], coef=self.coef, accumulate=True)
-            K.bn_bwd_apply_bnd(d, da, da2, y, M, self.scale, self.shift, act, dy)
-            return
         K.bn_bwd_finalize(part, nblk, self.C, M, self.gamma, self.save_mean, self.save_rstd, eng.G[self.prefix + ".weight"],
                           eng.G[self.prefix + ".bias"], self.coef, accumulate=True)
         K.bn_bwd_apply(da, da2, y, M, self.C, self.scale, self.shift, act, self.coef, dy)
@@ -975,20 +941,12 @@ class TSRNEngine(_EngineBase):
             gt1 = ws(t + "gt1", P1, 4 * Cc) if training else None      # GRU gate values [P][8 x hidden], kept for back-propagation
             gt2 = ws(t + "gt2", P1, 4 * Cc) if training else None
             part, _ = L["bn1"].partial(P1)
-            fin = L["bn1"].fin(P1, L["conv1"].b) if training else None      # finalized by the convolution's own launch
-            g1 = L["conv1"].fwd(N, H, W, cur, y1, bn_partial=part if training else None, bn_fin=fin, bn_coarse=training)
+            g1 = L["conv1"].fwd(N, H, W, cur, y1, bn_partial=part if training else None, bn_coarse=training)
+            L["bn1"].finalize(P1, L["conv1"].b, training, g1.bn_row_tiles)
             a1 = ws(t + "a1", P1, Cc)                   # mish(bn1(y1)) once: a 3x3 consumer would re-apply it 9x per element
-            dd = L["bn1"].derive_fwd(P1, L["conv1"].b, g1.bn_row_tiles) if (training and fin is None) else None
-            if dd is not None:                          # the materialising launch finalizes bn1 itself
-                K.affine_act_bnd(dd, y1, P1, "mish", a1)
-            else:
-                if fin is None:
-                    L["bn1"].finalize(P1, L["conv1"].b, training, g1.bn_row_tiles)
-                K.affine_act(y1, P1, Cc, L["bn1"].scale, L["bn1"].shift, "mish", a1)
-            fin = L["bn2"].fin(P1, L["conv2"].b) if training else None
-            g2 = L["conv2"].fwd(N, H, W, a1, y2, bn_partial=part if training else None, bn_fin=fin, bn_coarse=training)
-            if fin is None:
-                L["bn2"].finalize(P1, L["conv2"].b, training, g2.bn_row_tiles)
+            K.affine_act(y1, P1, Cc, L["bn1"].scale, L["bn1"].shift, "mish", a1)
+            g2 = L["conv2"].fwd(N, H, W, a1, y2, bn_partial=part if training else None, bn_coarse=training)
+            L["bn2"].finalize(P1, L["conv2"].b, training, g2.bn_row_tiles)
             if self.tl:   # torch.cat([bn2(y2), text strip], 1) inside the 1x1 conv's loader (model/tsrn.py:419-423)
                 L["gru1"].fwd(N, H, W, y2, gi1, h1, gt1, in_b=temb, cin_a=Cc, **L["bn2"].loader)
             else:
@@ -997,10 +955,8 @@ class TSRNEngine(_EngineBase):
             cur = out
         y7 = ws("y7", P1, Cc)
         part, _ = self.bn7.partial(P1)
-        fin = self.bn7.fin(P1, self.conv7.b) if training else None
-        g7 = self.conv7.fwd(N, H, W, cur, y7, bn_partial=part if training else None, bn_fin=fin, bn_coarse=training)
-        if fin is None:
-            self.bn7.finalize(P1, self.conv7.b, training, g7.bn_row_tiles)
+        g7 = self.conv7.fwd(N, H, W, cur, y7, bn_partial=part if training else None, bn_coarse=training)
+        self.bn7.finalize(P1, self.conv7.b, training, g7.bn_row_tiles)
         ups = ws("ups", 4 * P1, Cc)                      # pre-mish, pixel-shuffled [N][2H][2W][C]
         self.up.fwd(N, H, W, y7, ups, in2=b1, out_ps=True, **self.bn7.loader)
         mu = ws("mups", 4 * P1, Cc)                      # mish(ups) once (the 9-tap tail conv and its wgrad both read it)
@@ -1074,15 +1030,10 @@ class TSRNEngine(_EngineBase):
             s = ws(f"stn_s{i}", M, conv.Cout)
             part, _ = bn.partial(M)
             conv.fwd(N, h, w, cur, s, bn_partial=part)
-            dd = bn.derive_fwd(M, conv.b) if i < 5 else None
-            if dd is None:
-                bn.finalize(M, conv.b, True)
+            bn.finalize(M, conv.b, True)
             if i < 5:
                 a = ws(f"stn_a{i}", N * (h // ph) * (w // pw), conv.Cout)
-                if dd is not None:                      # the pooling launch finalizes this stage's BatchNorm itself
-                    K.affine_act_pool_bnd(dd, s, N, h, w, "relu", ph, pw, a)
-                else:
-                    K.affine_act_pool(s, N, h, w, conv.Cout, bn.scale, bn.shift, "relu", ph, pw, a)
+                K.affine_act_pool(s, N, h, w, conv.Cout, bn.scale, bn.shift, "relu", ph, pw, a)
                 cur = a
             else:
                 cur = s  # relu(bn(.)) of the last stage rides on fc1's loader

@@ -614,12 +614,10 @@ class ConvGeom:
 
 def make_conv_args(g: ConvGeom, inp, wt=None, out=None, *, bias=None, in2=None, in_scale=None, in_shift=None, in_act=None,
                    in_ps=False, in_ld=None, in_coff=0, in2_ld=None, out_act=None, out_ps=False, out_ld=None, out_coff=0,
-                   bn_partial=None, in_b=None, cin_a=0, in_b_ld=None, in_dil_w=1, wt_ld=0, wt_coff=0, stride_w=1, bnb=None, bn_fin=None,
+                   bn_partial=None, in_b=None, cin_a=0, in_b_ld=None, in_dil_w=1, wt_ld=0, wt_coff=0, stride_w=1, bnb=None,
                    bn_coarse=False, in2_scale=None) -> ConvArgs:
     """`bnb` (a dict from engine.BNLayer.fuse_stats): this convolution produces the gradient that enters a BatchNorm's backward pass --
-    its epilogue also writes that BatchNorm's two reduction sums per 64-pixel row block (tpgsr_conv_args.bnb_y).
-    `bn_fin` (a dict from engine.BNLayer.fin / fuse_stats(...)["fin"]): the launch also FINALIZES the BatchNorm whose statistics it
-    leaves in bn_partial -- by its last workgroup where the kernel can, by an appended launch otherwise (tpgsr_conv_args.fin_mode)"""
+    its epilogue also writes that BatchNorm's two reduction sums per 64-pixel row block (tpgsr_conv_args.bnb_y)."""
     a = ConvArgs()
     a.in_, a.in2, a.in_scale, a.in_shift = _p(inp), _p(in2), _p(in_scale), _p(in_shift)
     a.in2_scale = _p(in2_scale)        # a = in * in_scale + in_shift + in2 * in2_scale (whole-CU halo kernel only: conv_in2_scale_ok)
@@ -660,23 +658,10 @@ def make_conv_args(g: ConvGeom, inp, wt=None, out=None, *, bias=None, in2=None, 
         a.bnb_y, a.bnb_mean, a.bnb_rstd = _p(bnb["y"]), _p(bnb.get("mean")), _p(bnb.get("rstd"))
         a.bnb_scale, a.bnb_shift, a.bnb_act = _p(bnb.get("scale")), _p(bnb.get("shift")), act_code(bnb["act"])
         a.bnb_store_dz = int(bool(bnb.get("store_dz", False)))   # without "partial": a plain activation backward on the way out
-        if bn_fin is None:
-            bn_fin = bnb.get("fin")
-    if bn_fin is not None and BN_FIN_FUSE:
-        f = bn_fin
-        a.fin_mode, a.fin_count, a.fin_counter, a.fin_gamma = f["mode"], f["count"], _p(f["counter"]), _p(f["gamma"])
-        if f["mode"] == 1:
-            a.fin_beta, a.fin_bias = _p(f["beta"]), _p(f.get("bias"))
-            a.fin_scale, a.fin_shift, a.fin_mean, a.fin_rstd = _p(f["scale"]), _p(f["shift"]), _p(f.get("save_mean")), _p(f.get("save_rstd"))
-            a.fin_rm, a.fin_rv = _p(f.get("running_mean")), _p(f.get("running_var"))
-            a.fin_momentum, a.fin_eps = f.get("momentum", 0.1), f.get("eps", 1e-5)
-        else:
-            a.fin_scale, a.fin_shift, a.fin_mean = _p(f["coef"]), _p(f.get("dgamma")), _p(f.get("dbeta"))
-            a.fin_accumulate = int(bool(f.get("accumulate", True)))
     # bn_coarse (or bnb["coarse"]): whoever reduces the partial rows copes with ONE ROW PER 192 PIXELS when the launch lands on the
-    # whole-CU halo kernel (tpgsr_conv_args.bn_row_tiles; a third of the rows for every workgroup of a consumer that finalizes the
-    # BatchNorm itself, csrc/bn_derive.h); the caller reads the granularity back from `a.bn_row_tiles` / bnb["row_tiles"]
-    if (bn_coarse or (bnb is not None and bnb.get("coarse"))) and a.bn_partial and not a.fin_mode and BN_COARSE_ROWS and CONV_TERMS:
+    # whole-CU halo kernel (tpgsr_conv_args.bn_row_tiles: a third of the rows for the finalize launch); the caller reads the granularity
+    # back from `a.bn_row_tiles` / bnb["row_tiles"]
+    if (bn_coarse or (bnb is not None and bnb.get("coarse"))) and a.bn_partial and BN_COARSE_ROWS and CONV_TERMS:
         if _lib.load().tpgsr_conv_bn_row_tiles(C.byref(a)) == 3:
             a.bn_row_tiles = 3
     if bnb is not None:
@@ -696,18 +681,6 @@ def bn_rows(M: int, row_tiles: int = 1) -> int:
     """rows of a bn_partial buffer over M pixels at `row_tiles` 64-pixel blocks per row"""
     nblk = (M + 63) // 64
     return (nblk + max(1, row_tiles) - 1) // max(1, row_tiles)
-
-
-# BatchNorm finalize (forward statistics -> scale / shift; backward sums -> dgamma / dbeta / coefficients) as part of the convolution
-# launch that produces the partial sums: TPGSR_BN_FIN_FUSE=1.  OFF by default -- measured slower (C3 6.19 vs 6.08 ms per step,
-# profiles/r04aa_bn_fin_fuse_ab.md): the last workgroup of the whole-CU kernel reduces 393 KB of partial rows alone, through
-# L1-bypassing loads of write-through data, in ~14 us; the separate launch spreads the same reduction over 64 workgroups and costs
-# ~8 us including its launch boundary.  Correct and tested either way (tests/test_bn_fin_fuse_gpu.py).
-BN_FIN_FUSE = os.environ.get("TPGSR_BN_FIN_FUSE", "0") == "1"
-
-
-def bn_fin_fused() -> bool:
-    return bool(BN_FIN_FUSE and CONV_TERMS)
 
 
 # BatchNorm-backward reduction fused into the producing data-gradient convolution (TPGSR_BNB_FUSE=0: its own launch, as before)
@@ -942,69 +915,6 @@ def bn_bwd_finalize(partial, nblk, C_, count, gamma, save_mean, save_rstd, dgamm
 
 def bn_bwd_apply(da, da2, y, M, C_, scale, shift, act, coef, dy):
     _launch("tpgsr_bn_bwd_apply", _p(da), _p(da2), _p(y), M, C_, _p(scale), _p(shift), act_code(act), _p(coef), _p(dy))
-
-
-# BatchNorm finalized inside its first consumer's launch (csrc/bn_derive.h, round 5) instead of by tpgsr_bn_finalize / tpgsr_bn_bwd_finalize
-# launches of their own: the first ceil(C / 16) workgroups of the consumer's grid sum the partial rows and publish, everybody waits on a
-# flag.  OFF by default: three forms of "no finalize launch" were built and measured against the separate launches inside the C3 step
-# (profiles/r05e_bn_derive_ab.md) -- every workgroup summing the rows itself (256-thread workgroups: 6.34 vs 6.06 ms; one 1024-thread
-# workgroup per CU: 6.09 vs 5.93), and this deriver + flag hand-off (6.10 vs 5.99) -- and round 4's last-workgroup finalize before them
-# (6.19 vs 6.08): the separate 64-workgroup launch (3 us + a ~2 us boundary) is the cheapest way this chip has of putting a grid-wide
-# reduction between two launches.  TPGSR_BN_DERIVE=1 records the in-launch form (results agree to the last bit or two of scale / shift).
-BN_DERIVE = os.environ.get("TPGSR_BN_DERIVE", "0") == "1"
-
-
-def bn_derive_ok(C_: int, M: int = 1 << 30) -> bool:
-    """can a launch over an [M][C] map finalize its BatchNorm itself?  (channel counts the derivers split evenly; enough workgroups)"""
-    D = (C_ + 15) // 16
-    return BN_DERIVE and (C_ == 8 or (C_ % 16 == 0 and 16 <= C_ <= 512)) and M * C_ >= 1024 * D
-
-
-def plan_flag(device):
-    """one int32 word, zero when the launch that uses it starts: a fresh tensor for a direct call; inside a recorded plan a slot of the
-    plan's flag block, which the plan zeroes with ONE launch at its very start (inserted here when the first flag is asked for)"""
-    rec = _REC
-    if rec is None:
-        return torch.zeros(1, dtype=torch.int32, device=device)
-    if getattr(rec, "flags", None) is None:
-        rec.flags, rec.nflags = torch.zeros(128, dtype=torch.int32, device=device), 0
-        rec.keep.append(rec.flags)
-        rec.ops.insert(0, ["tpgsr_zero", getattr(_lib.load(), "tpgsr_zero"), [rec.flags.data_ptr(), 128], 0])
-        rec.dyn = {k: [(oi + 1, ai) for oi, ai in v] for k, v in rec.dyn.items()}      # every recorded op moved down by one
-        rec.meta = {oi + 1: v for oi, v in rec.meta.items()}
-    if rec.nflags >= rec.flags.numel():
-        raise RuntimeError("a recorded plan finalizes more than 128 BatchNorms inside their consumers")
-    rec.nflags += 1
-    return rec.flags[rec.nflags - 1:rec.nflags]
-
-
-def make_bn_derive(rows, nrows, C_, count, gamma, *, flag=None, bias=None, beta=None, running_mean=None, running_var=None, momentum=0.1,
-                   eps=1e-5, scale=None, shift=None, save_mean=None, save_rstd=None, dgamma=None, dbeta=None, coef=None, accumulate=False):
-    """flag: one zeroed int32 word (default: plan_flag -- a slot of the recorded plan's block, or a fresh tensor for a direct call, which
-    then serves ONE launch)"""
-    d = _lib.BnDerive()
-    if flag is None:
-        flag = plan_flag(rows.device if isinstance(rows, torch.Tensor) else None)
-    d._flag_keep = flag
-    d.rows, d.nrows, d.C, d.count = _p(rows), int(nrows), int(C_), int(count)
-    d.bias, d.gamma, d.beta = _p(bias), _p(gamma), _p(beta)
-    d.running_mean, d.running_var, d.momentum, d.eps = _p(running_mean), _p(running_var), momentum, eps
-    d.scale, d.shift, d.save_mean, d.save_rstd = _p(scale), _p(shift), _p(save_mean), _p(save_rstd)
-    d.dgamma, d.dbeta, d.coef, d.accumulate = _p(dgamma), _p(dbeta), _p(coef), int(bool(accumulate))
-    d.flag = _p(flag)
-    return d
-
-
-def affine_act_bnd(d, x, M, act, out):
-    _launch("tpgsr_affine_act_bnd", C.byref(d), _p(x), M, act_code(act), _p(out))
-
-
-def affine_act_pool_bnd(d, x, N, H, W, act, ph, pw, out):
-    _launch("tpgsr_affine_act_pool_bnd", C.byref(d), _p(x), N, H, W, act_code(act), ph, pw, _p(out))
-
-
-def bn_bwd_apply_bnd(d, da, da2, y, M, scale, shift, act, dy):
-    _launch("tpgsr_bn_bwd_apply_bnd", C.byref(d), _p(da), _p(da2), _p(y), M, _p(scale), _p(shift), act_code(act), _p(dy))
 
 
 def affine_act(x, M, C_, scale, shift, act, out):
