@@ -134,6 +134,41 @@ int tpgsr_conv_bn_row_tiles(const tpgsr_conv_args* a);
 
 int tpgsr_conv_fwd(const tpgsr_conv_args* a, void* stream);
 
+/* Which kernel tpgsr_conv_fwd(a) / tpgsr_conv_wgrad(w) runs under the current switches, and what its launcher decides on the host.  Host
+ * only (no device is needed); the launchers and the planners above and below are all written over this one decision (csrc/conv_route.h).
+ * Both return the kernel code and fill *r (-1: null pointer or a non-positive dimension); TPGSR_CONV_NONE / TPGSR_WGRAD_NONE: no kernel has this loader combination (the launch is refused). */
+enum tpgsr_conv_kernel {
+  TPGSR_CONV_NONE = 0,
+  TPGSR_CONV_F32_TILE = 1, TPGSR_CONV_F32_SCALAR = 2, TPGSR_CONV_F32_WSTAT = 3,         /* fp32 matrix cores: tile loop, scalar loader, weights-stationary 3x3 */
+  TPGSR_CONV_XBF_SPLITK = 4, TPGSR_CONV_XBF_HALO3 = 5, TPGSR_CONV_XBF_HALO = 6,         /* split-bf16: split-K, whole-CU halo, two-workgroup halo, */
+  TPGSR_CONV_XBF_PANEL = 7, TPGSR_CONV_XBF_TILE = 8                                     /* row panel, tile loop */
+};
+enum tpgsr_wgrad_kernel {
+  TPGSR_WGRAD_NONE = 0,
+  TPGSR_WGRAD_F32_TILE = 1, TPGSR_WGRAD_F32_SCALAR = 2,
+  TPGSR_WGRAD_XBF_HALO = 3, TPGSR_WGRAD_XBF_3K = 4, TPGSR_WGRAD_XBF_TILE = 5            /* split-bf16: halo, three k-blocks per workgroup, tile loop */
+};
+typedef struct tpgsr_conv_route_t {
+  int kernel;      /* enum tpgsr_conv_kernel */
+  int ld;          /* loader variant: 1 affine, 2 activation, 4 residual add, 8 pixel-shuffle gather, 16 concatenated strip, 32 scaled residual */
+  int lcap;        /* halo kernels: LDS entry capacity, else 0 */
+  int nbw;         /* panel kernel: 32-column blocks per wave, else 0 */
+  int lds_bytes;   /* dynamic LDS of the launch (weights-stationary, halo, panel kernels), else 0 */
+  int splits;      /* split-K: workgroups per tile (a->sk_splits), else 0 */
+  int sk_plan;     /* what tpgsr_conv_splitk_plan(a) proposes for sk_splits (0: do not split); independent of a->sk_splits */
+  int reserved;
+} tpgsr_conv_route_t;
+typedef struct tpgsr_wgrad_route_t {
+  int kernel;      /* enum tpgsr_wgrad_kernel */
+  int ld;
+  int lcap;        /* halo kernel: LDS entry capacity, else 0 */
+  int ne;          /* halo kernel: halo entries per producer thread, 7 or 9, else 0 */
+  int lds_bytes;   /* dynamic LDS of the launch (halo kernel), else 0 */
+  int Z, MB;       /* pixel splits, pixels per split */
+  int vecY;        /* dy rows are 16-byte aligned quads */
+} tpgsr_wgrad_route_t;
+int tpgsr_conv_route(const tpgsr_conv_args* a, tpgsr_conv_route_t* r);
+
 /* Weight-gradient GEMM:  part[z][k][n] = sum_{m in split z} A[m][k] * dy[m][n]   (A through the same
  * loader/prologue as tpgsr_conv_fwd), plus optional bias-gradient partials dbpart[z][n] = sum_m dy[m][n].
  * Replaces the cuDNN wgrad kernels autograd launches for every conv/linear above.
@@ -161,6 +196,7 @@ int tpgsr_wgrad_halo_plan(const tpgsr_conv_args* a, int* zsplits, long long* dy_
 /* (tpgsr_wgh_debug, the lab switch that turned parts of the halo weight-gradient kernel off, exists only in -DTPGSR_LAB builds of
  * csrc/conv_xbf.hip: tools/lab/wgh_probe.py) */
 int tpgsr_conv_wgrad(const tpgsr_wgrad_args* a, void* stream);
+int tpgsr_conv_wgrad_route(const tpgsr_wgrad_args* w, tpgsr_wgrad_route_t* r);
 /* Several independent weight-gradient GEMMs in ONE launch (the ten of the text-prior generator's two BiLSTM layers, model/crnn/crnn.py:5-26:
  * 25-65 us each alone -- start-up, not work).  items_dev: device-resident table; an item = the arguments of one tpgsr_conv_wgrad call plus
  * what its launcher derives from them, filled on the host by tpgsr_conv_wgrad_batch_prepare (returns the loader variant `ld`, >= 0, when
@@ -310,7 +346,6 @@ void tpgsr_halo_set_colmajor_min_bytes(long long v);
 /* smallest tap count (KH * KW) the halo forward kernel takes: 2 (default) or 1 (1x1 convolutions with Cin % 32 == 0 as well;
  * TPGSR_XBF_HALO_MINTAPS=1 at load time).  Results do not depend on it beyond fp32 summation order. */
 void tpgsr_halo_set_min_taps(int v);
-void tpgsr_halo_set_ne9(int on);   /* halos of 225..288 entries on the halo forward kernel as well (default off: slower than the tile loop; TPGSR_XBF_HALO_NE9) */
 /* The row-panel kernel of the 1x1 convolutions with K <= 192 over many pixels (csrc/conv_panel.hip: the GruBlock projections,
  * model/tsrn.py:491-508, and their data gradients): on / off (TPGSR_XBF_PANEL), and the smallest pixel count it takes (default 32768;
  * TPGSR_XBF_PANEL_MIN_M).  Placement of a launch on this kernel or on the tile loop only affects speed. */

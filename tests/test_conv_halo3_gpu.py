@@ -232,3 +232,30 @@ def test_coarse_statistics_rows_of_the_whole_cu_kernel(shape):
                 K.conv_fwd(a)
         finally:
             lib.tpgsr_halo3_set_enabled(1)
+
+
+@pytest.mark.parametrize("shape,with_switch", [((2, 8, 16, 32, 64, 3, 3, 1, 1), "xbf_halo"), ((48, 16, 64, 64, 64, 3, 3, 1, 1), "xbf_halo3")])
+def test_halo3_switch_reaches_the_launcher_through_the_route(shape, with_switch):
+    """tpgsr_halo3_set_enabled writes the knob the route reads, and the launcher runs what the route says: off and on give the same bits
+    (the comparison of test_halo3_bitwise_equals_two_workgroup_halo_kernel), on a 2 x 8 x 16 map of 32 -> 64 channels under x2 -- two
+    super-tiles, fewer than the whole-CU kernel asks for: the two-workgroup kernel either way -- and on the trunk shape, which moves"""
+    from tpgsr_amd import _lib, kernels as K
+    lib = _lib.load()
+    N, H, W, Ci, Co, KH, KW, ph, pw = shape
+    wf = torch.randn(KH * KW * Ci, Co, device=DEV)
+    with K.conv_terms(2):
+        K.make_bf_twin(wf, Ci)
+        a = K.make_conv_args(K.ConvGeom(*shape), torch.empty(N * H * W, Ci, device=DEV), wf, torch.empty(N * H * W, Co, device=DEV))
+    assert K.conv_route(a)[0] == with_switch
+    lib.tpgsr_halo3_set_enabled(0)
+    try:
+        assert K.conv_route(a)[0] == "xbf_halo"
+    finally:
+        lib.tpgsr_halo3_set_enabled(1)
+    o0, p0, ref = _run(*shape, terms=2, halo3=False, seed=3)
+    o1, p1, _ = _run(*shape, terms=2, halo3=True, seed=3)
+    err = ((o1.double().cpu() - ref).abs().max() / ref.abs().max()).item()
+    assert err < 5e-5
+    assert not torch.isnan(o1).any() and not torch.isnan(p1).any()
+    assert torch.equal(o1, o0), f"{(o1 != o0).sum().item()} outputs differ, max {(o1 - o0).abs().max().item():.3e}"
+    assert torch.equal(p1, p0), f"{(p1 != p0).sum().item()} statistics differ"

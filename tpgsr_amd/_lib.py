@@ -40,6 +40,20 @@ class WgradArgs(C.Structure):
                 ("zsplits", ci), ("reserved1", ci), ("dy_bf", vp)]
 
 
+class ConvRoute(C.Structure):
+    """tpgsr_conv_route_t: the kernel tpgsr_conv_fwd chooses (CONV_KERNELS) and what its launcher decides on the host"""
+    _fields_ = [("kernel", ci), ("ld", ci), ("lcap", ci), ("nbw", ci), ("lds_bytes", ci), ("splits", ci), ("sk_plan", ci), ("reserved", ci)]
+
+
+class WgradRoute(C.Structure):
+    """tpgsr_wgrad_route_t (WGRAD_KERNELS)"""
+    _fields_ = [("kernel", ci), ("ld", ci), ("lcap", ci), ("ne", ci), ("lds_bytes", ci), ("Z", ci), ("MB", ci), ("vecY", ci)]
+
+
+CONV_KERNELS = ("none", "f32_tile", "f32_scalar", "f32_wstat", "xbf_splitk", "xbf_halo3", "xbf_halo", "xbf_panel", "xbf_tile")
+WGRAD_KERNELS = ("none", "f32_tile", "f32_scalar", "xbf_halo", "xbf_3k", "xbf_tile")
+
+
 class GruWgradArgs(C.Structure):
     _fields_ = [("c", ConvArgs), ("dgi", vp), ("dghn", vp), ("h", vp), ("partC", vp), ("dbC", vp), ("partH", vp), ("dbH", vp),
                 ("axis", ci), ("zsplits", ci)]
@@ -110,6 +124,8 @@ _SIGS = {
     "tpgsr_version": (ci, []),
     "tpgsr_sizeof": (ci, [ci]),
     "tpgsr_conv_fwd": (ci, [C.POINTER(ConvArgs), vp]),
+    "tpgsr_conv_route": (ci, [C.POINTER(ConvArgs), C.POINTER(ConvRoute)]),
+    "tpgsr_conv_wgrad_route": (ci, [C.POINTER(WgradArgs), C.POINTER(WgradRoute)]),
     "tpgsr_bigru_proj_supported": (ci, [C.POINTER(BigruProjArgs)]),
     "tpgsr_bigru_proj_fwd": (ci, [C.POINTER(BigruProjArgs), vp]),
     "tpgsr_bigru_proj_set_enabled": (None, [ci]),
@@ -227,7 +243,6 @@ _SIGS = {
     "tpgsr_splitk_set_enabled": (None, [ci]),
     "tpgsr_halo_set_colmajor_min_bytes": (None, [C.c_longlong]),
     "tpgsr_halo_set_min_taps": (None, [ci]),
-    "tpgsr_halo_set_ne9": (None, [ci]),
     "tpgsr_halo3_set_enabled": (None, [ci]),
     "tpgsr_wgrad3_set_enabled": (None, [ci]),
     "tpgsr_panel_set_enabled": (None, [ci]),

@@ -17,11 +17,7 @@
 // first), so the two kernels agree bit for bit.  T <= 2 (three-term planes of 462 entries do not fit 160 KB twice): the fp32-equivalent
 // policy stays on the two-workgroup kernel.  Epilogue (bias / activation / BatchNorm statistics / BatchNorm-backward sums): xbf_store_tile.
 #include "conv_xbf_common.h"
-#include <mutex>
-#include <stdlib.h>
 #include <type_traits>
-#include <utility>
-#include <vector>
 
 // diagnostic time line (tpgsr_halo3_trace, as tpgsr_halo_trace of conv_xbf.hip): wall-clock stamps (100 MHz) of the first 8 workgroups,
 // [workgroup][8 wave rows][256 slots]; slot 4 j + k of item j -- producers: k = 0 loads issued, 1 split + stored, 2 past the barrier;
@@ -540,13 +536,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo3_xbf_kernel(tpgsr_conv_args 
   }
 }
 
-/* upper bound of the halo length of any run of 64 * H3_TM consecutive output pixels (cf. halo_capacity in conv_xbf.hip) */
-static int halo3_capacity(const tpgsr_conv_args* a) {
-  const int P = 64 * H3_TM, Wp = a->OW + a->KW - 1, ohw = a->OH * a->OW;
-  const int row_wraps = (a->OW % P == 0) ? 0 : (P - 1) / a->OW + 1;
-  const int img_wraps = (ohw % P == 0) ? 0 : (P - 1) / ohw + 1;
-  return P - 1 + row_wraps * (a->KW - 1) + img_wraps * (a->KH - 1) * Wp + (a->KH - 1) * Wp + a->KW;
-}
+static_assert(H3_TM == kH3Tiles && H3_NE == kH3Entries, "conv_route.h sizes this kernel's halo and LDS");
 
 extern "C" int tpgsr_halo3_trace(unsigned long long* buf) {   // buf: 8 * 8 * 256 uint64 of device memory, or nullptr to switch off
   if (hipMemcpyToSymbol(HIP_SYMBOL(g_halo3_trace), &buf, sizeof(buf)) != hipSuccess) {
@@ -556,62 +546,15 @@ extern "C" int tpgsr_halo3_trace(unsigned long long* buf) {   // buf: 8 * 8 * 25
   return 0;
 }
 
-static int g_h3_on = [] { const char* e = getenv("TPGSR_XBF_HALO3"); return (e && e[0] == '0') ? 0 : 1; }();
-/* experiment / test switch: 0 sends every convolution back to the two-workgroup halo kernel */
-extern "C" void tpgsr_halo3_set_enabled(int on) { g_h3_on = on ? 1 : 0; }
-
 #define H3_LD_CASES(X) X(0) X(1) X(2) X(3) X(4) X(5) X(7) X(37)
 
-// > 0 (the halo capacity) when the shape is this kernel's, else 0
-static int halo3_takes(const tpgsr_conv_args* a, long long M, int ld) {
-  const int T = a->terms;
-  if (!g_h3_on || T < 1 || T > 2 || a->KH * a->KW < 3 || !((a->KH * a->KW) & 1) || a->wt_bf_cin != a->Cin || (a->Cin & 31) || a->stride_w > 1 || a->in_dil_w > 1 || a->in_b ||
-      a->in_ps || ((ld & ~7) && ld != 37) || ld == 6 || a->OW + a->KW - 1 < 8)
-    return 0;
-  // the residual-add loader carries two quads per entry and has ONE register set (no load of the next block in flight), and a
-  // pixel-shuffled store goes out four bytes at a time: with both (the up-sampling convolution: 102 us here, 87 us there) the
-  // two-workgroup kernel, whose second workgroup covers those waits, is faster
-  if ((ld & 4) && a->out_ps) return 0;
-  const int Lcap = halo3_capacity(a);
-  const size_t lds = (size_t)2 * T * H3_PLANE + 2 * H3_TM * 1024 + 8 * 4096;      // halo buffers + statistics scratch + epilogue staging (161 792 B at T = 2)
-  if (Lcap > 32 * H3_NE || lds > 163840) return 0;
-  // one round of the chip (or several full ones): with fewer super-tiles than CUs the two-workgroup kernel spreads the work better
-  const long long nst = (long long)cdiv(cdiv(M, 64), H3_TM) * cdiv(a->Cout, 64);
-  static const long long min_st = [] { const char* e = getenv("TPGSR_XBF_HALO3_MIN"); return e ? atoll(e) : 192ll; }();
-  if (nst < min_st) return 0;
-  switch (ld) {
-#define H3_OK(B) case B:
-    H3_LD_CASES(H3_OK)
-#undef H3_OK
-    return Lcap;
-    default: return 0;
-  }
-}
-
-/* (launcher-internal, conv_xbf.hip's split-K plan) does this kernel take the launch? */
-extern "C" int tpgsr_conv_halo3_would_take(const tpgsr_conv_args* a, long long M, int ld) { return halo3_takes(a, M, ld) > 0 ? 1 : 0; }
-
-/* 1 when a launch with a scaled residual operand (tpgsr_conv_args.in2_scale) is this kernel's -- the only one whose loader has it */
-extern "C" int tpgsr_conv_in2_scale_ok(const tpgsr_conv_args* a) {
-  if (!a || !(a->terms > 0 && a->wt_bf && (a->Cin & 3) == 0 && (a->wt_coff & 31) == 0) || !a->in2 || !a->in_scale || a->in_act || a->in_b) return 0;
-  return halo3_takes(a, (long long)a->N * a->OH * a->OW, 37) > 0 ? 1 : 0;
-}
-
-/* tpgsr_conv_args.bn_row_tiles: 3 when tpgsr_conv_fwd(a) lands here (the dispatch of conv_mfma.hip / conv_xbf.hip up to this kernel) */
-extern "C" int tpgsr_conv_bn_row_tiles(const tpgsr_conv_args* a) {
-  if (!a || !(a->terms > 0 && a->wt_bf && (a->Cin & 3) == 0 && (a->wt_coff & 31) == 0)) return 1;
-  const int ld = (a->in_scale ? 1 : 0) | (a->in_act ? 2 : 0) | (a->in2 ? 4 : 0) | (a->in_ps ? 8 : 0) | (a->in_b ? 16 : 0);
-  return halo3_takes(a, (long long)a->N * a->OH * a->OW, ld) > 0 ? H3_TM : 1;
-}
-
-// returns 1 when launched, 0 when the shape is not this kernel's, < 0 on error
-extern "C" int tpgsr_conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M, int ld, hipStream_t st) {
-  const int T = a->terms;
-  const int Lcap = halo3_takes(a, M, ld);
-  if (Lcap <= 0) return 0;
+// one workgroup per CU on three 64-pixel tiles at once; tpgsr_halo3_set_enabled(0) / TPGSR_XBF_HALO3=0 sends every convolution back to the
+// two-workgroup halo kernel
+int conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M, const tpgsr_conv_route_t& r, hipStream_t st) {
+  const int T = a->terms, ld = r.ld, Lcap = r.lcap;
   TPGSR_CHECK_ARG(a->bn_row_tiles == 0 || a->bn_row_tiles == 1 || a->bn_row_tiles == H3_TM,
                   "tpgsr_conv_fwd(halo3): bn_row_tiles %d (0, 1 or %d)", a->bn_row_tiles, H3_TM);
-  const size_t lds = (size_t)2 * T * H3_PLANE + 2 * H3_TM * 1024 + 8 * 4096;
+  const size_t lds = r.lds_bytes;      // halo buffers + statistics scratch + epilogue staging
   const long long nst = (long long)cdiv(cdiv(M, 64), H3_TM) * cdiv(a->Cout, 64);
   const void* fn = nullptr;
   const bool t9 = a->KH * a->KW == 9;
@@ -622,7 +565,7 @@ extern "C" int tpgsr_conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M
     break;
   switch (ld) {
     H3_LD_CASES(H3_CASE)
-    default: return 0;
+    default: return unsupported_ld("tpgsr_conv_fwd", ld);
   }
 #undef H3_CASE
   int dev = 0, cus = 0;
@@ -630,21 +573,8 @@ extern "C" int tpgsr_conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M
     tpgsr_set_error("tpgsr_conv_fwd(halo3): device query failed");
     return TPGSR_ERR_LAUNCH;
   }
-  {   // opt-in to > 64 KB of dynamic LDS, per (kernel, device): raised to the largest size seen so far
-    static std::mutex mu;
-    static std::vector<std::pair<std::pair<const void*, int>, size_t>> done;
-    std::lock_guard<std::mutex> lock(mu);
-    size_t* cur = nullptr;
-    for (auto& d : done)
-      if (d.first.first == fn && d.first.second == dev) cur = &d.second;
-    if (!cur || *cur < lds) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        tpgsr_set_error("tpgsr_conv_fwd(halo3): LDS opt-in (%zu bytes) failed", lds);
-        return TPGSR_ERR_LAUNCH;
-      }
-      if (cur) *cur = lds; else done.push_back({{fn, dev}, lds});
-    }
-  }
+  const int rc = lds_opt_in(fn, lds, "tpgsr_conv_fwd(halo3)");
+  if (rc) return rc;
   dim3 grid((unsigned)(nst < cus ? nst : cus));      // persistent: one workgroup per CU
   int Mi = (int)M, Lc = Lcap;
   tpgsr_conv_args args = *a;
@@ -653,5 +583,16 @@ extern "C" int tpgsr_conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M
     tpgsr_set_error("tpgsr_conv_fwd(halo3): launch failed: %s", hipGetErrorString(hipGetLastError()));
     return TPGSR_ERR_LAUNCH;
   }
-  return 1;
+  TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd(bf16 MFMA, whole-CU halo)");
+}
+
+/* (tests/test_conv_halo3_gpu.py's guard against a silent fall-through) launches when tpgsr_conv_fwd(a) would run on this kernel: 1 when it
+ * did, 0 when the launch is another kernel's, < 0 on error.  `ld` is unused (the route computes the loader variant): it
+ * stays in the signature the test binds */
+extern "C" int tpgsr_conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M, int ld, hipStream_t st) {
+  (void)ld;
+  const tpgsr_conv_route_t r = conv_fwd_route(a, M);
+  if (r.kernel != TPGSR_CONV_XBF_HALO3) return 0;
+  const int rc = conv_halo3_xbf_launch(a, M, r, st);
+  return rc < 0 ? rc : 1;
 }

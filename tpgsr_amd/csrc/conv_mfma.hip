@@ -9,7 +9,6 @@
 // second operand row-major in LDS; v_mfma_f32_32x32x2_f32 fragments are fetched with conflict-free ds_read_b32
 // (lane l reads row k0 + (l>>5), column (l&31)).  fp32 in, fp32 accumulate: bit-for-bit an fmaf chain.
 #include "common.h"
-#include <stdlib.h>
 #include <mutex>
 
 // 1: all MFMA fragments of a K chunk are read from LDS before its first MFMA (one LDS round trip per chunk, +32 VGPRs:
@@ -18,14 +17,17 @@
 #ifndef TPGSR_FRAG_PRELOAD
 #define TPGSR_FRAG_PRELOAD 0
 #endif
+#include <utility>
+#include <vector>
 #include "conv_loader.h"
+#include "conv_launch.h"
 
 // ------------------------------------------------------------------------------------------------------
 // forward / data-gradient kernel
 // ------------------------------------------------------------------------------------------------------
-// SPLIT = 2: two 256-thread groups per workgroup work on the two halves of the K range of the SAME 64x64 tile (own LDS
-// buffers, combined through LDS at the end).  Used for grids of only a few tiles per CU (the 64->64 convs: 768 tiles):
-// it doubles the resident wavefronts per SIMD without shrinking the MFMA tile.
+// SPLIT: 1 in every instantiation.  (SPLIT = 2 -- two 256-thread groups per workgroup on the two halves of the K range of the SAME 64x64
+// tile, combined through LDS -- measured neutral and is no longer built or dispatched: DESIGN.md "Retired experiments".  The parameter
+// stays because taking it out of the text changes the register allocation of two of the ten instantiations.)
 template <int LD, int SPLIT>   // LD >= 0: vector quad loader with compile-time prologue bits; LD < 0: generic scalar loader
 __global__ __launch_bounds__(256 * SPLIT) void conv_fwd_kernel(tpgsr_conv_args a, int M, int K, int vecB) {
   constexpr bool VEC_A = LD >= 0;
@@ -315,9 +317,36 @@ __global__ __launch_bounds__(768) void conv3x3_wstat_kernel(tpgsr_conv_args a, c
   }
 }
 
-extern "C" int tpgsr_conv_fwd_xbf_launch(const tpgsr_conv_args* a, long long M, int K, int ld, hipStream_t st);
-extern "C" int tpgsr_conv_wgrad_xbf_launch(const tpgsr_wgrad_args* w, long long M, int K, int Z, int MB, int ld, hipStream_t st);
-extern "C" int tpgsr_conv_wgrad_halo_launch(const tpgsr_wgrad_args* w, long long M, int ld, hipStream_t st);
+static_assert(sizeof(float) * WS_LDS_FLOATS == kWstatLdsBytes, "conv_route.h sizes the weights-stationary kernel's LDS");
+
+int unsupported_ld(const char* who, int ld) {
+  tpgsr_set_error("%s: unsupported loader combination %d", who, ld);
+  return TPGSR_ERR_ARG;
+}
+
+// opt-in to > 64 KB of dynamic LDS, per (kernel, device): raised to the largest size seen so far
+int lds_opt_in(const void* fn, size_t bytes, const char* who) {
+  if (bytes <= 64 * 1024) return 0;
+  static std::mutex mu;
+  static std::vector<std::pair<std::pair<const void*, int>, size_t>> done;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    tpgsr_set_error("%s: hipGetDevice failed", who);
+    return TPGSR_ERR_LAUNCH;
+  }
+  std::lock_guard<std::mutex> lock(mu);
+  size_t* cur = nullptr;
+  for (auto& d : done)
+    if (d.first.first == fn && d.first.second == dev) cur = &d.second;
+  if (!cur || *cur < bytes) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
+      tpgsr_set_error("%s: LDS opt-in (%zu bytes) failed", who, bytes);
+      return TPGSR_ERR_LAUNCH;
+    }
+    if (cur) *cur = bytes; else done.push_back({{fn, dev}, bytes});
+  }
+  return 0;
+}
 
 static int check_conv_args(const tpgsr_conv_args* a, const char* who) {
   TPGSR_CHECK_ARG(a && a->in, "%s: null input", who);
@@ -347,11 +376,6 @@ static int check_conv_args(const tpgsr_conv_args* a, const char* who) {
   return 0;
 }
 
-// compile-time loader variant: 1 affine, 2 activation, 4 residual add, 8 pixel-shuffle gather
-static int loader_bits(const tpgsr_conv_args* a) {
-  return (a->in_scale ? 1 : 0) | (a->in_act ? 2 : 0) | (a->in2 ? 4 : 0) | (a->in_ps ? 8 : 0) | (a->in_b ? 16 : 0) | (a->in2_scale ? 32 : 0);
-}
-
 extern "C" int tpgsr_conv_fwd(const tpgsr_conv_args* a, void* stream) {
   int rc = check_conv_args(a, "tpgsr_conv_fwd");
   if (rc) return rc;
@@ -363,11 +387,7 @@ extern "C" int tpgsr_conv_fwd(const tpgsr_conv_args* a, void* stream) {
   long long M = (long long)a->N * a->OH * a->OW;
   int K = a->KH * a->KW * a->Cin;
   TPGSR_CHECK_ARG(M < (1ll << 31), "tpgsr_conv_fwd: M too large");
-  dim3 grid(cdiv(M, BM) * cdiv(a->Cout, BN));
-  const int wld_ = a->wt_ld > 0 ? a->wt_ld : a->Cout;
-  int vecB = ((wld_ & 3) == 0 && ((uintptr_t)a->wt & 15) == 0) ? 1 : 0;   // rows padded to a multiple of 4 floats
   hipStream_t st = (hipStream_t)stream;
-  const int ld = loader_bits(a);
   if (a->bnb_y) {   // BatchNorm-backward statistics / activation backward in the epilogue
     TPGSR_CHECK_ARG(!a->out_ps && !a->bias && a->out_act == TPGSR_ACT_NONE,
                     "tpgsr_conv_fwd: bnb_y goes with a plain dense data-gradient store (no bias, no output activation, no pixel shuffle)");
@@ -379,76 +399,80 @@ extern "C" int tpgsr_conv_fwd(const tpgsr_conv_args* a, void* stream) {
     else
       TPGSR_CHECK_ARG(a->bnb_store_dz, "tpgsr_conv_fwd: bnb_y without bn_partial and without bnb_store_dz does nothing");
   }
-  // bf16 matrix cores with split operands (conv_xbf.hip): vector loader + pre-split weights required
-  if (a->terms > 0 && a->wt_bf && (a->Cin & 3) == 0 && (a->wt_coff & 31) == 0) {
+  const bool xbf = xbf_eligible(a);   // bf16 matrix cores with split operands: vector loader + pre-split weights required
+  if (xbf) {
     TPGSR_CHECK_ARG(a->terms >= 1 && a->terms <= 3, "tpgsr_conv_fwd: terms must be 0, 1, 2 or 3");
     TPGSR_CHECK_ARG(a->kp >= K && (a->kp & 31) == 0 && ((uintptr_t)a->wt_bf & 15) == 0, "tpgsr_conv_fwd: bad split operand (kp %d, K %d)", a->kp, K);
-    return tpgsr_conv_fwd_xbf_launch(a, M, K, ld, st);
-  }
-  TPGSR_CHECK_ARG(a->bn_row_tiles <= 1, "tpgsr_conv_fwd: bn_row_tiles %d needs the whole-CU halo kernel (split-bf16 path)", a->bn_row_tiles);
-  TPGSR_CHECK_ARG(!a->bnb_y, "tpgsr_conv_fwd: the BatchNorm-backward epilogue (bnb_y) exists in the split-bf16 kernels only (terms > 0, wt_bf, Cin %% 4 == 0)");
-  // the 64-channel 3x3 trunk convs on 64-wide maps: weights-stationary kernel (TPGSR_CONV_WSTAT=0 falls back to the tile loop)
-  static const bool wstat_on = [] { const char* e = getenv("TPGSR_CONV_WSTAT"); return !(e && e[0] == '0'); }();
-  if (wstat_on && ld == 0 && a->KH == 3 && a->KW == 3 && a->pad_h == 1 && a->pad_w == 1 && a->Cin == 64 && a->Cout == 64 &&
-      a->W == 64 && a->OW == 64 && a->OH == a->H && a->in_dil_w <= 1 && a->stride_w <= 1 && !a->out_ps && a->out_act == TPGSR_ACT_NONE &&
-      (a->wt_ld == 0 || a->wt_ld == 64) && a->wt_coff == 0 && (a->in_ld & 3) == 0 && (a->in_coff & 3) == 0 &&
-      (((uintptr_t)a->in | (uintptr_t)a->wt) & 15) == 0) {
-    // per device, set up once under a lock: 256 B of zeros (source of the halo's padding pixels; zeroed on the launch
-    // stream and waited for, so every later launch on any stream sees it) and the opt-in to > 64 KB of dynamic LDS
-    static float* zero_page[64] = {nullptr};
-    static std::mutex init_mu;
-    const size_t lds = sizeof(float) * WS_LDS_FLOATS;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-      tpgsr_set_error("tpgsr_conv_fwd: hipGetDevice failed");
-      return TPGSR_ERR_LAUNCH;
-    }
-    {
-      std::lock_guard<std::mutex> lock(init_mu);
-      if (!zero_page[dev]) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-          tpgsr_set_error("tpgsr_conv_fwd: first use of the weights-stationary conv on device %d happens inside a stream capture; "
-                          "run one eager step before capturing", dev);
-          return TPGSR_ERR_LAUNCH;
-        }
-        float* zp = nullptr;
-        if (hipMalloc((void**)&zp, 256) != hipSuccess || hipMemsetAsync(zp, 0, 256, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess ||
-            hipFuncSetAttribute((const void*)conv3x3_wstat_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-          tpgsr_set_error("tpgsr_conv_fwd: zero page / %zu-byte LDS set-up failed", lds);
-          return TPGSR_ERR_LAUNCH;
-        }
-        zero_page[dev] = zp;
-      }
-    }
-    const int rows = (int)(M / 64);
-    hipLaunchKernelGGL(conv3x3_wstat_kernel, dim3((rows + 2) / 3), dim3(768), lds, st, *a, zero_page[dev], (int)M);
-    TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd");
-  }
-  vecB = vecB && ((a->wt_coff & 3) == 0);
-  // optional (TPGSR_CONV_SPLITK=1): split K over two thread groups of one workgroup (twice the resident waves on grids
-  // of few tiles per CU).  Measured neutral on MI355X for the 768-tile 64->64 convs (48.0 vs 47.4 us): the launch is
-  // bound by per-launch fixed costs, not by occupancy, so it is off by default.
-  const char* splitk = getenv("TPGSR_CONV_SPLITK");
-  const bool split = splitk && splitk[0] == '1' && grid.x < 256 * 5 && (K + KC - 1) / KC >= 6;
-#define TPGSR_FWD_CASE(B)                                                                                \
-  case B:                                                                                                \
-    if (split) hipLaunchKernelGGL((conv_fwd_kernel<B, 2>), grid, dim3(512), 0, st, *a, (int)M, K, vecB); \
-    else hipLaunchKernelGGL((conv_fwd_kernel<B, 1>), grid, dim3(256), 0, st, *a, (int)M, K, vecB);       \
-    break;
-  if ((a->Cin & 3) != 0 || !vecB) {
-    hipLaunchKernelGGL((conv_fwd_kernel<-1, 1>), grid, dim3(256), 0, st, *a, (int)M, K, vecB);
+    TPGSR_CHECK_ARG(a->wt_bf_cin == 0 || (a->wt_bf_cin == a->Cin && (a->Cin & 31) == 0),
+                    "tpgsr_conv_fwd: weights were split in channel-block order for Cin %d, the convolution has Cin %d", a->wt_bf_cin, a->Cin);
   } else {
-    switch (ld) {
-      TPGSR_FWD_CASE(0) TPGSR_FWD_CASE(1) TPGSR_FWD_CASE(3) TPGSR_FWD_CASE(4) TPGSR_FWD_CASE(5) TPGSR_FWD_CASE(7)
-      TPGSR_FWD_CASE(8) TPGSR_FWD_CASE(2) TPGSR_FWD_CASE(17)
-      default:
-        tpgsr_set_error("tpgsr_conv_fwd: unsupported loader combination %d", ld);
-        return TPGSR_ERR_ARG;
-    }
+    TPGSR_CHECK_ARG(a->bn_row_tiles <= 1, "tpgsr_conv_fwd: bn_row_tiles %d needs the whole-CU halo kernel (split-bf16 path)", a->bn_row_tiles);
+    TPGSR_CHECK_ARG(!a->bnb_y, "tpgsr_conv_fwd: the BatchNorm-backward epilogue (bnb_y) exists in the split-bf16 kernels only (terms > 0, wt_bf, Cin %% 4 == 0)");
   }
+  const tpgsr_conv_route_t r = conv_fwd_route(a, M);
+  if (xbf && a->sk_splits <= 1 && r.kernel != TPGSR_CONV_XBF_HALO3) {      // (an explicit split count never reached these two checks)
+    TPGSR_CHECK_ARG(!(r.ld & 32), "tpgsr_conv_fwd: a scaled residual operand (in2_scale) exists in the whole-CU halo kernel's loader only, which does not "
+                    "take this launch (ask tpgsr_conv_in2_scale_ok first)");
+    TPGSR_CHECK_ARG(a->bn_row_tiles <= 1, "tpgsr_conv_fwd: bn_row_tiles %d is the whole-CU halo kernel's, which does not take this launch "
+                    "(ask tpgsr_conv_bn_row_tiles first)", a->bn_row_tiles);
+  }
+  dim3 grid(cdiv(M, BM) * cdiv(a->Cout, BN));
+  switch (r.kernel) {
+    case TPGSR_CONV_XBF_SPLITK:
+    case TPGSR_CONV_XBF_TILE: return conv_fwd_xbf_launch(a, M, K, r, st);
+    case TPGSR_CONV_XBF_HALO3: return conv_halo3_xbf_launch(a, M, r, st);
+    case TPGSR_CONV_XBF_HALO: return conv_halo_xbf_launch(a, M, r, st);
+    case TPGSR_CONV_XBF_PANEL: return conv_panel_xbf_launch(a, M, r, st);
+    case TPGSR_CONV_F32_WSTAT: {   // the 64-channel 3x3 trunk convs on 64-wide maps (TPGSR_CONV_WSTAT=0 falls back to the tile loop)
+      // per device, set up once under a lock: 256 B of zeros (source of the halo's padding pixels; zeroed on the launch
+      // stream and waited for, so every later launch on any stream sees it)
+      static float* zero_page[64] = {nullptr};
+      static std::mutex init_mu;
+      int dev = 0;
+      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
+        tpgsr_set_error("tpgsr_conv_fwd: hipGetDevice failed");
+        return TPGSR_ERR_LAUNCH;
+      }
+      {
+        std::lock_guard<std::mutex> lock(init_mu);
+        if (!zero_page[dev]) {
+          hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+          if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+            tpgsr_set_error("tpgsr_conv_fwd: first use of the weights-stationary conv on device %d happens inside a stream capture; "
+                            "run one eager step before capturing", dev);
+            return TPGSR_ERR_LAUNCH;
+          }
+          float* zp = nullptr;
+          if (hipMalloc((void**)&zp, 256) != hipSuccess || hipMemsetAsync(zp, 0, 256, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            tpgsr_set_error("tpgsr_conv_fwd: zero page set-up failed");
+            return TPGSR_ERR_LAUNCH;
+          }
+          zero_page[dev] = zp;
+        }
+      }
+      rc = lds_opt_in((const void*)conv3x3_wstat_kernel, r.lds_bytes, "tpgsr_conv_fwd(weights-stationary)");
+      if (rc) return rc;
+      const int rows = (int)(M / 64);
+      hipLaunchKernelGGL(conv3x3_wstat_kernel, dim3((rows + 2) / 3), dim3(768), r.lds_bytes, st, *a, zero_page[dev], (int)M);
+      break;
+    }
+    case TPGSR_CONV_F32_SCALAR: {
+      const int wld = a->wt_ld > 0 ? a->wt_ld : a->Cout;
+      const int vecB = ((wld & 3) == 0 && ((uintptr_t)a->wt & 15) == 0 && (a->wt_coff & 3) == 0) ? 1 : 0;   // rows padded to a multiple of 4 floats
+      hipLaunchKernelGGL((conv_fwd_kernel<-1, 1>), grid, dim3(256), 0, st, *a, (int)M, K, vecB);
+      break;
+    }
+    case TPGSR_CONV_F32_TILE:
+#define TPGSR_FWD_CASE(B) case B: hipLaunchKernelGGL((conv_fwd_kernel<B, 1>), grid, dim3(256), 0, st, *a, (int)M, K, 1); break;
+      switch (r.ld) {
+        TPGSR_FWD_CASE(0) TPGSR_FWD_CASE(1) TPGSR_FWD_CASE(3) TPGSR_FWD_CASE(4) TPGSR_FWD_CASE(5) TPGSR_FWD_CASE(7)
+        TPGSR_FWD_CASE(8) TPGSR_FWD_CASE(2) TPGSR_FWD_CASE(17)
+        default: return unsupported_ld("tpgsr_conv_fwd", r.ld);
+      }
 #undef TPGSR_FWD_CASE
+      break;
+    default: return unsupported_ld("tpgsr_conv_fwd", r.ld);
+  }
   TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd");
 }
 
@@ -458,6 +482,7 @@ extern "C" int tpgsr_conv_fwd(const tpgsr_conv_args* a, void* stream) {
 #define WK 64  // k rows per block
 #define WM 32  // pixels per staged chunk
 #define WALD (WM + 1)
+static_assert(KC == kConvKC && BN == kConvBN && WK == kWgradWK && WM == kWgradWM, "conv_route.h plans splits over these tiles");
 
 __device__ __forceinline__ float4 load_dy4(const tpgsr_wgrad_args& w, const PixelPos& p, int m, int col, int vec) {
   const tpgsr_conv_args& a = w.c;
@@ -606,33 +631,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(tpgsr_wgrad_args w, int
   if (want_db && n0 + tid < a.Cout) w.dbpart[(size_t)zblk * a.Cout + n0 + tid] = dbacc;
 }
 
-static void wgrad_plan(long long M, int K, int Cout, int* Z, int* MB) {
-  int kb = cdiv(K, WK), nb = cdiv(Cout, BN);
-  // ~4 blocks per CU (TPGSR_WGRAD_TARGET: experiment switch -- fewer, longer splits write fewer slabs for the reduce to read back)
-  static const long long target_env = [] { const char* e = getenv("TPGSR_WGRAD_TARGET"); return e ? atoll(e) : 0ll; }();
-  long long target = target_env > 0 ? target_env : 1024;
-  long long z = (target + (long long)kb * nb - 1) / ((long long)kb * nb);
-  long long maxz = (M + 255) / 256;  // at least 256 pixels per split
-  if (maxz > 256) maxz = 256;
-  if (z > maxz) z = maxz;
-  if (z < 1) z = 1;
-  long long mb = (M + z - 1) / z;
-  mb = (mb + WM - 1) / WM * WM;
-  z = (M + mb - 1) / mb;
-  *Z = (int)z;
-  *MB = (int)mb;
-}
-
-/* (internal, for conv_xbf.hip's batched launch: the split count / pixels per split and the loader variant tpgsr_conv_wgrad uses) */
-extern "C" void tpgsr_wgrad_plan_host(long long M, int K, int Cout, int* Z, int* MB) { wgrad_plan(M, K, Cout, Z, MB); }
-extern "C" int tpgsr_loader_bits(const tpgsr_conv_args* a) { return loader_bits(a); }
-
-extern "C" int tpgsr_wgrad_splits(int M, int K, int Cout) {
-  int Z, MB;
-  wgrad_plan(M, K, Cout, &Z, &MB);
-  return Z;
-}
-
 extern "C" int tpgsr_conv_wgrad(const tpgsr_wgrad_args* w, void* stream) {
   TPGSR_CHECK_ARG(w != nullptr, "tpgsr_conv_wgrad: null args");
   int rc = check_conv_args(&w->c, "tpgsr_conv_wgrad");
@@ -645,38 +643,26 @@ extern "C" int tpgsr_conv_wgrad(const tpgsr_wgrad_args* w, void* stream) {
   int K = a->KH * a->KW * a->Cin;
   TPGSR_CHECK_ARG(M < (1ll << 31) && M * (w->dy_ps ? a->Cout : w->dy_ld) * 4 <= 0x7fffffffll,
                   "tpgsr_conv_wgrad: dy exceeds the 2 GiB buffer-addressing window (M %lld)", M);
-  int Z, MB;
-  wgrad_plan(M, K, a->Cout, &Z, &MB);
-  if (w->zsplits > 0) {   // the caller's split count: whole 64-pixel tiles per split (what the halo kernel walks)
-    Z = w->zsplits;
-    MB = cdiv(cdiv(M, 64), Z) * 64;
-  }
-  dim3 grid(cdiv(K, WK) * cdiv(a->Cout, BN) * Z);
-  // rows padded to a multiple of 4 floats keep an odd channel count (the 37 classes) on the vector path: the loads of the
-  // last quad stay inside the padded row, columns >= Cout are never stored
-  int vecY = (!w->dy_ps && (w->dy_ld & 3) == 0 && (w->dy_coff & 3) == 0 && w->dy_ld >= ((a->Cout + 3) & ~3) + w->dy_coff &&
-              ((uintptr_t)w->dy & 15) == 0) ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
-  const int ld = loader_bits(a);
-  if (a->terms > 0 && (a->Cin & 3) == 0 && (vecY || w->dy_ps)) {
+  const tpgsr_wgrad_route_t r = conv_wgrad_route(w, M);
+  if (a->terms > 0 && (a->Cin & 3) == 0 && (r.vecY || w->dy_ps))   // the split-bf16 kernels
     TPGSR_CHECK_ARG(a->terms >= 1 && a->terms <= 3, "tpgsr_conv_wgrad: terms must be 0, 1, 2 or 3");
-    const int h = tpgsr_conv_wgrad_halo_launch(w, M, ld, st);
-    if (h < 0) return h;
-    if (h > 0) TPGSR_LAUNCH_CHECK("tpgsr_conv_wgrad(bf16 MFMA, halo)");
-    return tpgsr_conv_wgrad_xbf_launch(w, M, K, Z, MB, ld, st);
-  }
-#define TPGSR_WG_CASE(B) case B: hipLaunchKernelGGL(conv_wgrad_kernel<B>, grid, dim3(256), 0, st, *w, (int)M, K, MB, vecY); break;
-  if ((a->Cin & 3) != 0 || (!vecY && !w->dy_ps)) {
-    hipLaunchKernelGGL(conv_wgrad_kernel<-1>, grid, dim3(256), 0, st, *w, (int)M, K, MB, vecY);
-  } else {
-    switch (ld) {
-      TPGSR_WG_CASE(0) TPGSR_WG_CASE(1) TPGSR_WG_CASE(3) TPGSR_WG_CASE(4) TPGSR_WG_CASE(5) TPGSR_WG_CASE(7) TPGSR_WG_CASE(2) TPGSR_WG_CASE(17)
-      default:
-        tpgsr_set_error("tpgsr_conv_wgrad: unsupported loader combination %d", ld);
-        return TPGSR_ERR_ARG;
-    }
-  }
+  dim3 grid(cdiv(K, WK) * cdiv(a->Cout, BN) * r.Z);
+  switch (r.kernel) {
+    case TPGSR_WGRAD_XBF_HALO: return conv_wgrad_halo_launch(w, M, r, st);
+    case TPGSR_WGRAD_XBF_3K:
+    case TPGSR_WGRAD_XBF_TILE: return conv_wgrad_xbf_launch(w, M, K, r, st);
+    case TPGSR_WGRAD_F32_SCALAR: hipLaunchKernelGGL(conv_wgrad_kernel<-1>, grid, dim3(256), 0, st, *w, (int)M, K, r.MB, r.vecY); break;
+    case TPGSR_WGRAD_F32_TILE:
+#define TPGSR_WG_CASE(B) case B: hipLaunchKernelGGL(conv_wgrad_kernel<B>, grid, dim3(256), 0, st, *w, (int)M, K, r.MB, r.vecY); break;
+      switch (r.ld) {
+        TPGSR_WG_CASE(0) TPGSR_WG_CASE(1) TPGSR_WG_CASE(3) TPGSR_WG_CASE(4) TPGSR_WG_CASE(5) TPGSR_WG_CASE(7) TPGSR_WG_CASE(2) TPGSR_WG_CASE(17)
+        default: return unsupported_ld("tpgsr_conv_wgrad", r.ld);
+      }
 #undef TPGSR_WG_CASE
+      break;
+    default: return unsupported_ld("tpgsr_conv_wgrad", r.ld);
+  }
   TPGSR_LAUNCH_CHECK("tpgsr_conv_wgrad");
 }
 

@@ -16,11 +16,7 @@
 //   * epilogue shared with the tile loop (bias, activation, pixel-shuffle store, BN partial statistics).
 // 768 workgroups at M = 49152: one resident round at three workgroups per CU.
 #include "conv_xbf_common.h"
-#include <stdlib.h>
-#include <mutex>
 #include <type_traits>
-#include <utility>
-#include <vector>
 
 // NBW: 32-column blocks per wave (the workgroup covers 64 NBW columns); NQ8 = K / 32 = quads per thread and pixel row
 template <int LD, int T, int NBW, int NQ8>
@@ -124,52 +120,17 @@ __global__ __launch_bounds__(256, 2) void conv_panel_xbf_kernel(tpgsr_conv_args 
   xbf_epilogue<1, NBW>(a, acc, M, m0, 0, mblk, wm, wn, lane, tid, red, red + 4 * 64 * NBW + wave * 1024);
 }
 
-static int g_panel_on = [] { const char* e = getenv("TPGSR_XBF_PANEL"); return !(e && e[0] == '0') ? 1 : 0; }();
-/* experiment / test switch: 0 sends the 1x1 convolutions back to the tile loop */
-extern "C" void tpgsr_panel_set_enabled(int on) { g_panel_on = on ? 1 : 0; }
-
-static long long g_panel_min_m = [] { const char* e = getenv("TPGSR_XBF_PANEL_MIN_M"); return e ? atoll(e) : 32768ll; }();
-/* smallest pixel count the panel kernel takes (default 32768 = 512 workgroups; below that the tile loop's column split fills more of the chip) */
-extern "C" void tpgsr_panel_set_min_m(long long m) { g_panel_min_m = m < 64 ? 64 : m; }
-
-// K = 192 -> <= 64 columns (the projections' data gradients): measured on MI355X 22.0 us against 20.2 us on the tile loop in x3 arithmetic
-// (two 77 KB workgroups per CU, no overlap inside a workgroup), 15.3 us in x2 -- off unless TPGSR_XBF_PANEL_K192=1
-static int g_panel_k192 = [] { const char* e = getenv("TPGSR_XBF_PANEL_K192"); return (e && e[0] == '1') ? 1 : 0; }();
-extern "C" void tpgsr_panel_set_k192(int on) { g_panel_k192 = on ? 1 : 0; }
-
-// (K / 32, 32-column blocks per wave) pairs instantiated: 64 -> <= 192, 96 -> <= 192, 192 -> <= 64
+// (K / 32, 32-column blocks per wave) pairs instantiated: 64 -> <= 192, 96 -> <= 192, 192 -> <= 64 (the last: measured on MI355X 22.0 us
+// against 20.2 us on the tile loop in x3 arithmetic -- two 77 KB workgroups per CU, no overlap inside a workgroup -- 15.3 us in x2: off
+// unless TPGSR_XBF_PANEL_K192=1 / tpgsr_panel_set_k192(1)).  tpgsr_panel_set_enabled(0) sends the 1x1 convolutions back to the tile loop;
+// tpgsr_panel_set_min_m: smallest pixel count the kernel takes (default 32768 = 512 workgroups; below that the tile loop's column split
+// fills more of the chip)
 #define PANEL_LD_CASES(X) X(0) X(1) X(4) X(17)
 
-// 32-column blocks per wave when the shape is this kernel's, else 0
-static int panel_takes(const tpgsr_conv_args* a, long long M, int ld) {
-  const int T = a->terms;
-  if (!g_panel_on || a->KH * a->KW != 1 || a->wt_bf_cin != 0 || a->stride_w > 1 || a->in_dil_w > 1 || a->in_ps || a->pad_h || a->pad_w ||
-      a->OH != a->H || a->OW != a->W || M < g_panel_min_m || T < 1 || T > 3)
-    return 0;
-  const int nb32 = (a->Cout + 31) >> 5, nq8 = a->kp >> 5;
-  int nbw = 0;
-  if ((nq8 == 2 || nq8 == 3) && nb32 <= 6) nbw = 3;
-  else if (nq8 == 6 && nb32 <= 2 && g_panel_k192) nbw = 1;
-  else return 0;
-  switch (ld) {
-#define PANEL_OK(B) case B:
-    PANEL_LD_CASES(PANEL_OK)
-#undef PANEL_OK
-    return nbw;
-    default: return 0;
-  }
-}
-/* (launcher-internal, conv_xbf.hip's split-K plan) */
-extern "C" int tpgsr_conv_panel_would_take(const tpgsr_conv_args* a, long long M, int ld) { return panel_takes(a, M, ld) > 0 ? 1 : 0; }
-
-// returns 1 when launched, 0 when the shape is not this kernel's, < 0 on error
-extern "C" int tpgsr_conv_panel_xbf_launch(const tpgsr_conv_args* a, long long M, int ld, hipStream_t st) {
-  const int T = a->terms;
-  const int nbw = panel_takes(a, M, ld);
-  if (nbw <= 0) return 0;
+int conv_panel_xbf_launch(const tpgsr_conv_args* a, long long M, const tpgsr_conv_route_t& r, hipStream_t st) {
+  const int T = a->terms, ld = r.ld;
   const int nq8 = a->kp >> 5;
-  size_t lds = (size_t)T * 64 * (nq8 * 64 + 16);
-  if (lds < (size_t)(4 * 64 * nbw + 4 * 1024) * 4) lds = (size_t)(4 * 64 * nbw + 4 * 1024) * 4;      // (epilogue scratch: statistics + staging)
+  const size_t lds = r.lds_bytes;      // the panel, or the epilogue's scratch (statistics + staging) where that is larger
   const void* fn = nullptr;
 #define PANEL_PICK(B, TT)                                                          \
   fn = nq8 == 2 ? (const void*)conv_panel_xbf_kernel<B, TT, 3, 2>                  \
@@ -183,29 +144,13 @@ extern "C" int tpgsr_conv_panel_xbf_launch(const tpgsr_conv_args* a, long long M
     break;
   switch (ld) {
     PANEL_LD_CASES(PANEL_CASE)
-    default: return 0;
+    default: return unsupported_ld("tpgsr_conv_fwd", ld);
   }
 #undef PANEL_CASE
 #undef PANEL_PICK
-  if (lds > 64 * 1024) {   // opt-in to > 64 KB of dynamic LDS, per (kernel, device)
-    static std::mutex mu;
-    static std::vector<std::pair<const void*, int>> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-      tpgsr_set_error("tpgsr_conv_fwd(panel): hipGetDevice failed");
-      return TPGSR_ERR_LAUNCH;
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    bool have = false;
-    for (auto& d : done) have = have || (d.first == fn && d.second == dev);
-    if (!have) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        tpgsr_set_error("tpgsr_conv_fwd(panel): LDS opt-in failed");
-        return TPGSR_ERR_LAUNCH;
-      }
-      done.push_back({fn, dev});
-    }
-  }
+  // (a kernel's panel size is fixed by its template arguments -- terms, K / 32, blocks per wave -- so its LDS limit is raised once)
+  const int rc = lds_opt_in(fn, lds, "tpgsr_conv_fwd(panel)");
+  if (rc) return rc;
   tpgsr_conv_args args = *a;
   int Mi = (int)M;
   void* params[] = {&args, &Mi};
@@ -213,5 +158,5 @@ extern "C" int tpgsr_conv_panel_xbf_launch(const tpgsr_conv_args* a, long long M
     tpgsr_set_error("tpgsr_conv_fwd(panel): launch failed: %s", hipGetErrorString(hipGetLastError()));
     return TPGSR_ERR_LAUNCH;
   }
-  return 1;
+  TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd(bf16 MFMA, panel)");
 }

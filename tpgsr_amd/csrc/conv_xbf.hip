@@ -20,8 +20,6 @@
 //   rows padded to 192 B; the contraction runs over pixels, so fragments are fetched with the transposing
 //   ds_read_b64_tr_b16 (4 consecutive pixels of one channel per lane and instruction).
 #include "conv_loader.h"
-#include <stdlib.h>
-#include <stdio.h>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -649,100 +647,26 @@ extern "C" int tpgsr_halo_trace(unsigned long long* buf) {   // buf: 8 * 8 * 256
   return 0;
 }
 
-// upper bound of the halo length of any 64-pixel tile (see the kernel's header)
-static int halo_capacity(const tpgsr_conv_args* a) {
-  const int Wp = a->OW + a->KW - 1, ohw = a->OH * a->OW;
-  const int row_wraps = (a->OW % 64 == 0) ? 0 : 63 / a->OW + 1;
-  const int img_wraps = (ohw % 64 == 0) ? 0 : 63 / ohw + 1;
-  return 63 + row_wraps * (a->KW - 1) + img_wraps * (a->KH - 1) * Wp + (a->KH - 1) * Wp + a->KW;
-}
-
-extern "C" int tpgsr_halo_capacity(const tpgsr_conv_args* a) { return a ? halo_capacity(a) : -1; }   // (host-only; tests/test_halo_host_cpu.py)
-
-static long long g_nmajor_min_bytes = 3ll << 20;
-/* weight-plane size above which the halo forward kernel walks its tiles column-major per XCD (-1: never; 0: whenever the column-tile
- * count allows); default 3 MB */
-extern "C" void tpgsr_halo_set_colmajor_min_bytes(long long v) { g_nmajor_min_bytes = v; }
-
-/* smallest tap count the halo kernel takes (default 2; 1 sends 1x1 convolutions with Cin % 32 == 0 through it as well --
- * TPGSR_XBF_HALO_MINTAPS, experiment switch) */
-static int g_halo_force_ne9 = 0;
-/* tests: let the halo forward kernel take halos of 225..288 entries (its 9-entries-per-thread variant) */
-extern "C" void tpgsr_halo_set_ne9(int on) { g_halo_force_ne9 = on ? 1 : 0; }
-static int g_halo_min_taps = [] { const char* e = getenv("TPGSR_XBF_HALO_MINTAPS"); return e && e[0] == '1' ? 1 : 2; }();
-extern "C" void tpgsr_halo_set_min_taps(int v) { g_halo_min_taps = v < 1 ? 1 : v; }
-
 #define XBF_HALO_LD_CASES(X) X(0) X(1) X(2) X(3) X(4) X(5) X(7)
 
-// returns 1 when launched, 0 when the shape is not one of the halo kernel's, < 0 on error
-// does the two-workgroup halo kernel take this launch?  0: no; else the halo capacity (`small`: the 7-entries-per-thread variant)
-static int halo_takes(const tpgsr_conv_args* a, int ld, bool* small_out) {
-  static const bool on = [] { const char* e = getenv("TPGSR_XBF_HALO"); return !(e && e[0] == '0'); }();
-  const int T = a->terms;
-  if (!on || a->KH * a->KW < g_halo_min_taps || (a->wt_bf_cin != a->Cin && !(a->KH * a->KW == 1 && a->wt_bf_cin == 0)) || (a->Cin & 31) || a->stride_w > 1 || a->in_dil_w > 1 ||
-      a->in_b || ((ld & ~7) && ld != 8) || ld == 6 || a->OW + a->KW - 1 < 8)
-    return 0;
-  const int Lcap = halo_capacity(a);
-  const size_t lds = (size_t)2 * T * Lcap * 64 + 2048;      // two halo buffers + two 1 KB statistics scratch areas
-  // two workgroups per CU or not at all: with one, nothing covers a workgroup's barriers and epilogues (the 16x50 recognizer
-  // conv, 278 halo entries = 107 KB in x3 mode, measured 54 us here against 47 us on the tile loop)
-  if (Lcap > 32 * 9 || lds > 80 * 1024) return 0;
-  const bool small = Lcap <= 32 * 7;
-  // the 9-entries-per-thread variant (halos of 225..288 entries: the recognizer's 16 x 50 maps).  In x3 arithmetic its two 107 KB
-  // buffers never fit (rejected above); in x2 / bf16 they do (73 KB) and the launch was measured at 203 us against ~45 us on the tile
-  // loop (128 -> 64 data gradient at batch 48, profiles/r03j_kernel_stats_c3_x2.md) -- off unless TPGSR_XBF_HALO_NE9=1
-  static const bool ne9 = [] { const char* e = getenv("TPGSR_XBF_HALO_NE9"); return e && e[0] == '1'; }();
-  if (!small && !ne9 && !g_halo_force_ne9) return 0;
-  switch (ld) {
-#define XBF_HALO_OK(B) case B:
-    XBF_HALO_LD_CASES(XBF_HALO_OK)
-#undef XBF_HALO_OK
-    case 8: break;
-    default: return 0;
-  }
-  if (small_out) *small_out = small;
-  return Lcap;
-}
-
-static int conv_halo_xbf_launch(const tpgsr_conv_args* a, long long M, int ld, hipStream_t st) {
-  const int T = a->terms;
-  bool small = false;
-  const int Lcap = halo_takes(a, ld, &small);
-  if (Lcap <= 0) return 0;
-  const size_t lds = (size_t)2 * T * Lcap * 64 + 2048;      // two halo buffers + two 1 KB statistics scratch areas
+int conv_halo_xbf_launch(const tpgsr_conv_args* a, long long M, const tpgsr_conv_route_t& r, hipStream_t st) {
+  const int T = a->terms, ld = r.ld, Lcap = r.lcap;
+  const size_t lds = r.lds_bytes;      // two halo buffers + two 1 KB statistics scratch areas
   const void* fn = nullptr;
-#define XBF_HALO_CASE(B)                                                                                                      \
-  case B:                                                                                                                     \
-    fn = T == 1 ? (small ? (const void*)conv_halo_xbf_kernel<B, 1, 7> : (const void*)conv_halo_xbf_kernel<B, 1, 9>)           \
-       : T == 2 ? (small ? (const void*)conv_halo_xbf_kernel<B, 2, 7> : (const void*)conv_halo_xbf_kernel<B, 2, 9>)           \
-                : (small ? (const void*)conv_halo_xbf_kernel<B, 3, 7> : (const void*)conv_halo_xbf_kernel<B, 3, 9>);          \
+#define XBF_HALO_CASE(B)                                                                     \
+  case B:                                                                                    \
+    fn = T == 1 ? (const void*)conv_halo_xbf_kernel<B, 1, 7>                                 \
+       : T == 2 ? (const void*)conv_halo_xbf_kernel<B, 2, 7>                                 \
+                : (const void*)conv_halo_xbf_kernel<B, 3, 7>;                                \
     break;
   switch (ld) {
     XBF_HALO_LD_CASES(XBF_HALO_CASE)
     XBF_HALO_CASE(8)        // plain un-PixelShuffle gather (the data gradient of the upsample block's convolution)
-    default: return 0;
+    default: return unsupported_ld("tpgsr_conv_fwd", ld);
   }
 #undef XBF_HALO_CASE
-  if (lds > 64 * 1024) {   // opt-in to > 64 KB of dynamic LDS, per (kernel, device): raised to the largest size seen so far
-    static std::mutex mu;
-    static std::vector<std::pair<std::pair<const void*, int>, size_t>> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-      tpgsr_set_error("tpgsr_conv_fwd: hipGetDevice failed");
-      return TPGSR_ERR_LAUNCH;
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    size_t* cur = nullptr;
-    for (auto& d : done)
-      if (d.first.first == fn && d.first.second == dev) cur = &d.second;
-    if (!cur || *cur < lds) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        tpgsr_set_error("tpgsr_conv_fwd: LDS opt-in (%zu bytes) for the halo kernel failed", lds);
-        return TPGSR_ERR_LAUNCH;
-      }
-      if (cur) *cur = lds; else done.push_back({{fn, dev}, lds});
-    }
-  }
+  const int rc = lds_opt_in(fn, lds, "tpgsr_conv_fwd(halo)");
+  if (rc) return rc;
   // persistent grid: as many workgroups as the chip holds at once (occupancy x CUs), cached per (kernel, LDS size, device)
   struct Occ { const void* fn; size_t lds; int dev, wgs; };
   static std::mutex omu;
@@ -766,10 +690,6 @@ static int conv_halo_xbf_launch(const tpgsr_conv_args* a, long long M, int ld, h
       }
       resident = per_cu * cus;
       occ.push_back({fn, lds, dev, resident});
-      static const bool dbg = [] { const char* e = getenv("TPGSR_XBF_DEBUG"); return e && e[0] == '1'; }();
-      if (dbg)
-        fprintf(stderr, "[tpgsr] halo conv: Cin %d Cout %d %dx%d ld %d T %d Lcap %d lds %zu -> %d workgroups/CU x %d CUs\n", a->Cin, a->Cout,
-                a->KH, a->KW, ld, T, Lcap, lds, per_cu, cus);
     }
   }
   const long long ntiles = (long long)cdiv(M, 64) * cdiv(a->Cout, 64);
@@ -779,133 +699,52 @@ static int conv_halo_xbf_launch(const tpgsr_conv_args* a, long long M, int ld, h
   // column-major tile order per XCD when the split weight planes would not stay in a 4 MB L2 next to the activations
   const int nbn = cdiv(a->Cout, 64);
   const long long w_bytes = (long long)T * a->kp * cdiv(a->Cout, 32) * 32 * 2;
-  args.reserved0 = (g_nmajor_min_bytes >= 0 && w_bytes > g_nmajor_min_bytes && (nbn % 8 == 0 || 8 % nbn == 0) && nbn > 1 && (grid.x % 8 == 0 || grid.x == ntiles)) ? 1 : 0;
+  args.reserved0 = (g_conv_knobs.colmajor_min_bytes >= 0 && w_bytes > g_conv_knobs.colmajor_min_bytes && (nbn % 8 == 0 || 8 % nbn == 0) && nbn > 1 && (grid.x % 8 == 0 || grid.x == ntiles)) ? 1 : 0;
   void* params[] = {&args, &Mi, &Lc};
   if (hipLaunchKernel(fn, grid, dim3(512), params, lds, st) != hipSuccess) {
     tpgsr_set_error("tpgsr_conv_fwd(halo): launch failed: %s", hipGetErrorString(hipGetLastError()));
     return TPGSR_ERR_LAUNCH;
   }
-  return 1;
+  TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd(bf16 MFMA, halo)");
 }
 
-// wave-tile choice of the tile loop (WMB x 1 blocks of 32 x 32 per wave; workgroup tile 64 WMB x 64).  TPGSR_XBF_TILE=11|21 forces one.
-static int xbf_fwd_tile(long long M, int Cout) {
-  static const int force = [] { const char* e = getenv("TPGSR_XBF_TILE"); return e ? atoi(e) : 0; }();
-  if (force == 11 || force == 21) return force;
-  return 11;
-}
-
-extern "C" int tpgsr_conv_panel_xbf_launch(const tpgsr_conv_args* a, long long M, int ld, hipStream_t st);
-extern "C" int tpgsr_conv_halo3_xbf_launch(const tpgsr_conv_args* a, long long M, int ld, hipStream_t st);   // conv_halo3.hip
-
-// ---- split-K (tpgsr_conv_args.sk_splits) ----
-// on by default (C3 x2 interleaved on one box: 5.391 / 5.380 -> 5.363 / 5.340 ms per step, family replay 4.29 -> 4.15 ms; the STN head's
-// 96-pixel convolutions 32 -> 13 us, InfoGen's 512 -> 128 47 -> 31, the BiLSTM projections' data gradients 34 / 30 -> 29 / 20);
-// TPGSR_XBF_SPLITK=0 / tpgsr_splitk_set_enabled(0): every launch unsplit
-static int g_sk_on = [] { const char* e = getenv("TPGSR_XBF_SPLITK"); return (e && e[0] == '0') ? 0 : 1; }();
-extern "C" void tpgsr_splitk_set_enabled(int on) { g_sk_on = on ? 1 : 0; }
-extern "C" int tpgsr_conv_halo3_would_take(const tpgsr_conv_args* a, long long M, int ld);    // conv_halo3.hip
-extern "C" int tpgsr_conv_panel_would_take(const tpgsr_conv_args* a, long long M, int ld);    // conv_panel.hip
-
-// launches with fewer tiles than ~2/3 of the CUs and >= 24 K chunks: S workgroups per tile so that ~640 are resident, >= 6 chunks each
-static int splitk_choice(long long M, int Cout, int kp) {
-  static const int target = [] { const char* e = getenv("TPGSR_XBF_SPLITK_TARGET"); return e ? atoi(e) : 640; }();      // resident workgroups aimed at
-  static const int min_cps = [] { const char* e = getenv("TPGSR_XBF_SPLITK_MIN_CHUNKS"); return e ? atoi(e) : 6; }();   // chunks per split at least
-  static const int max_tiles = [] { const char* e = getenv("TPGSR_XBF_SPLITK_MAX_TILES"); return e ? atoi(e) : 256; }();
-  static const int min_k = [] { const char* e = getenv("TPGSR_XBF_SPLITK_MIN_K"); return e ? atoi(e) : 24; }();          // K chunks of the launch at least
-  const long long ntiles = cdiv(M, 64) * cdiv(Cout, 64);
-  const int nchunks = kp / KC;
-  if (ntiles > max_tiles || nchunks < min_k) return 0;
-  int S = (int)(target / ntiles);
-  S = S < 2 ? 2 : S > 8 ? 8 : S;
-  int cps = (nchunks + S - 1) / S;
-  if (cps < min_cps) cps = min_cps;
-  S = (nchunks + cps - 1) / cps;          // no empty split
-  return S > 1 ? S : 0;
-}
-
-extern "C" int tpgsr_conv_splitk_plan(const tpgsr_conv_args* a, long long* bytes) {
-  if (bytes) *bytes = 0;
-  if (!a || !g_sk_on || !(a->terms > 0 && a->terms <= 3 && a->wt_bf && (a->Cin & 3) == 0 && (a->wt_coff & 31) == 0) || a->bn_row_tiles > 1 || a->in2_scale)
-    return 0;
-  const int ld = (a->in_scale ? 1 : 0) | (a->in_act ? 2 : 0) | (a->in2 ? 4 : 0) | (a->in_ps ? 8 : 0) | (a->in_b ? 16 : 0);
-  switch (ld) {
-#define XBF_SK_OK(B) case B:
-    XBF_LD_CASES(XBF_SK_OK)
-#undef XBF_SK_OK
-    break;
-    default: return 0;
-  }
-  const long long M = (long long)a->N * a->OH * a->OW;
-  // (a launch the two-workgroup halo kernel would take is split all the same -- conv6, 2 x 2 over 1248 pixels: 36.7 -> 31.3 us in x3,
-  //  28.9 -> 23.5 in x2 -- unless TPGSR_XBF_SPLITK_OVER_HALO=0; an explicit sk_splits wins in the launcher)
-  static const int over_halo = [] { const char* e = getenv("TPGSR_XBF_SPLITK_OVER_HALO"); return (e && e[0] == '0') ? 0 : 1; }();
-  if (tpgsr_conv_halo3_would_take(a, M, ld) || (!over_halo && halo_takes(a, ld, nullptr) > 0) || tpgsr_conv_panel_would_take(a, M, ld)) return 0;
-  const int S = splitk_choice(M, a->Cout, a->kp);
-  if (S > 1 && bytes) *bytes = (long long)S * cdiv(M, 64) * cdiv(a->Cout, 64) * 256 * 16 * 4;
-  return S;
-}
-
-extern "C" int tpgsr_conv_fwd_xbf_launch(const tpgsr_conv_args* a, long long M, int K, int ld, hipStream_t st) {
-  const int T = a->terms;
-  TPGSR_CHECK_ARG(a->wt_bf_cin == 0 || (a->wt_bf_cin == a->Cin && (a->Cin & 31) == 0),
-                  "tpgsr_conv_fwd: weights were split in channel-block order for Cin %d, the convolution has Cin %d", a->wt_bf_cin, a->Cin);
-  if (a->sk_splits > 1) {       // split-K: S workgroups per tile + the reduce / epilogue launch (the caller asked tpgsr_conv_splitk_plan)
-    TPGSR_CHECK_ARG(a->sk_part && a->sk_splits <= 64 && a->sk_splits <= a->kp / KC && ((uintptr_t)a->sk_part & 15) == 0,
-                    "tpgsr_conv_fwd: sk_splits %d needs sk_part (16-byte aligned) and at most one split per K chunk (%d)", a->sk_splits, a->kp / KC);
+// ---- split-K (tpgsr_conv_args.sk_splits) and the tile loop ----
+// split-K is on by default (C3 x2 interleaved on one box: 5.391 / 5.380 -> 5.363 / 5.340 ms per step, family replay 4.29 -> 4.15 ms; the STN
+// head's 96-pixel convolutions 32 -> 13 us, InfoGen's 512 -> 128 47 -> 31, the BiLSTM projections' data gradients 34 / 30 -> 29 / 20);
+// TPGSR_XBF_SPLITK=0 / tpgsr_splitk_set_enabled(0): tpgsr_conv_splitk_plan proposes no split
+int conv_fwd_xbf_launch(const tpgsr_conv_args* a, long long M, int K, const tpgsr_conv_route_t& r, hipStream_t st) {
+  const int T = a->terms, ld = r.ld;
+  if (r.kernel == TPGSR_CONV_XBF_SPLITK) {       // S workgroups per tile + the reduce / epilogue launch (the caller asked tpgsr_conv_splitk_plan)
+    TPGSR_CHECK_ARG(a->sk_part && r.splits <= 64 && r.splits <= a->kp / KC && ((uintptr_t)a->sk_part & 15) == 0,
+                    "tpgsr_conv_fwd: sk_splits %d needs sk_part (16-byte aligned) and at most one split per K chunk (%d)", r.splits, a->kp / KC);
     const unsigned ntile = (unsigned)(cdiv(M, 64) * cdiv(a->Cout, 64));
-    dim3 gsk(ntile * (unsigned)a->sk_splits);
-#define XBF_SK_CASE(B)                                                                                                   \
-  case B:                                                                                                                \
+    dim3 gsk(ntile * (unsigned)r.splits);
+#define XBF_SK_CASE(B)                                                                                                \
+  case B:                                                                                                             \
     if (T == 1) hipLaunchKernelGGL((conv_fwd_xbf_kernel<B, 1, 1, 1, 1>), gsk, dim3(256), 0, st, *a, (int)M, K);          \
     else if (T == 2) hipLaunchKernelGGL((conv_fwd_xbf_kernel<B, 2, 1, 1, 1>), gsk, dim3(256), 0, st, *a, (int)M, K);     \
     else hipLaunchKernelGGL((conv_fwd_xbf_kernel<B, 3, 1, 1, 1>), gsk, dim3(256), 0, st, *a, (int)M, K);                 \
     break;
     switch (ld) {
       XBF_LD_CASES(XBF_SK_CASE)
-      default:
-        tpgsr_set_error("tpgsr_conv_fwd: unsupported loader combination %d", ld);
-        return TPGSR_ERR_ARG;
+      default: return unsupported_ld("tpgsr_conv_fwd", ld);
     }
 #undef XBF_SK_CASE
     hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(ntile), dim3(256), 0, st, *a, (int)M);
     TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd(bf16 MFMA, split-K)");
   }
-  const int h3 = tpgsr_conv_halo3_xbf_launch(a, M, ld, st);      // whole-CU kernel: three tiles per workgroup, one round of the chip
-  if (h3 < 0) return h3;
-  if (h3 > 0) TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd(bf16 MFMA, whole-CU halo)");
-  TPGSR_CHECK_ARG(!(ld & 32), "tpgsr_conv_fwd: a scaled residual operand (in2_scale) exists in the whole-CU halo kernel's loader only, which does not "
-                  "take this launch (ask tpgsr_conv_in2_scale_ok first)");
-  TPGSR_CHECK_ARG(a->bn_row_tiles <= 1, "tpgsr_conv_fwd: bn_row_tiles %d is the whole-CU halo kernel's, which does not take this launch "
-                  "(ask tpgsr_conv_bn_row_tiles first)", a->bn_row_tiles);
-  const int h = conv_halo_xbf_launch(a, M, ld, st);
-  if (h < 0) return h;
-  if (h > 0) TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd(bf16 MFMA, halo)");
-  const int pn = tpgsr_conv_panel_xbf_launch(a, M, ld, st);       // conv_panel.hip: 1x1 convolutions with a short K over many pixels
-  if (pn < 0) return pn;
-  if (pn > 0) TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd(bf16 MFMA, panel)");
-  const int cfg = xbf_fwd_tile(M, a->Cout);
-  const int wmb = cfg / 10;
-  dim3 grid(cdiv(M, 64 * wmb) * cdiv(a->Cout, 64));
-#define XBF_FWD_T(B, TT)                                                                                                    \
-  switch (cfg) {                                                                                                            \
-    case 21: hipLaunchKernelGGL((conv_fwd_xbf_kernel<B, TT, 2, 1>), grid, dim3(256), 0, st, *a, (int)M, K); break;          \
-    default: hipLaunchKernelGGL((conv_fwd_xbf_kernel<B, TT, 1, 1>), grid, dim3(256), 0, st, *a, (int)M, K); break;          \
-  }
-#define XBF_FWD_CASE(B)                  \
-  case B:                                \
-    if (T == 1) { XBF_FWD_T(B, 1) }      \
-    else if (T == 2) { XBF_FWD_T(B, 2) } \
-    else { XBF_FWD_T(B, 3) }             \
+  dim3 grid(cdiv(M, 64) * cdiv(a->Cout, 64));
+#define XBF_FWD_CASE(B)                                                                                               \
+  case B:                                                                                                             \
+    if (T == 1) hipLaunchKernelGGL((conv_fwd_xbf_kernel<B, 1, 1, 1>), grid, dim3(256), 0, st, *a, (int)M, K);         \
+    else if (T == 2) hipLaunchKernelGGL((conv_fwd_xbf_kernel<B, 2, 1, 1>), grid, dim3(256), 0, st, *a, (int)M, K);    \
+    else hipLaunchKernelGGL((conv_fwd_xbf_kernel<B, 3, 1, 1>), grid, dim3(256), 0, st, *a, (int)M, K);                \
     break;
   switch (ld) {
     XBF_LD_CASES(XBF_FWD_CASE)
-    default:
-      tpgsr_set_error("tpgsr_conv_fwd: unsupported loader combination %d", ld);
-      return TPGSR_ERR_ARG;
+    default: return unsupported_ld("tpgsr_conv_fwd", ld);
   }
 #undef XBF_FWD_CASE
-#undef XBF_FWD_T
   TPGSR_LAUNCH_CHECK("tpgsr_conv_fwd(bf16 MFMA)");
 }
 
@@ -914,6 +753,7 @@ extern "C" int tpgsr_conv_fwd_xbf_launch(const tpgsr_conv_args* a, long long M, 
 // ------------------------------------------------------------------------------------------------------
 #define WK 64
 #define WM 32
+static_assert(KC == kConvKC && BN == kConvBN && WK == kWgradWK && WM == kWgradWM, "conv_route.h plans splits over these tiles");
 
 // transposing fragment fetch: 8 consecutive pixels (contraction index) of channel `col0 + (lane & 31)` from a pixel-major
 // [32 pixels][64 channels] bf16 image.  One ds_read_b64_tr_b16 hands lane l the column (l & 15) of the [4 pixels][16 channels]
@@ -929,9 +769,6 @@ __device__ __forceinline__ bf16x8 frag_tr(const unsigned char* plane, int lane, 
   s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(bf16x8, v);
 }
-
-extern "C" void tpgsr_wgrad_plan_host(long long M, int K, int Cout, int* Z, int* MB);   // conv_mfma.hip
-extern "C" int tpgsr_loader_bits(const tpgsr_conv_args* a);
 
 // (bx of gx: this workgroup's index within ITS launch -- the whole grid, or one item's share of a batched launch)
 template <int LD, int T>
@@ -1246,10 +1083,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_xbf3_kernel(tpgsr_wgrad_args w
   }
 }
 
-static int g_wg3_on = [] { const char* e = getenv("TPGSR_XBF_WGRAD3"); return (e && e[0] == '0') ? 0 : 1; }();
-/* experiment / test switch: 0 sends every tile-loop weight gradient back to the one-block kernel */
-extern "C" void tpgsr_wgrad3_set_enabled(int on) { g_wg3_on = on ? 1 : 0; }
-
 // Several INDEPENDENT weight-gradient GEMMs in one launch (a device-resident item table, like the pack / reduce programs).  The two
 // BiLSTM layers of the text-prior generator have ten of them -- 2 directions x (hidden side, input side) + the embedding, per layer --
 // over M = N T = 1248 rows each: a launch alone is 25-65 us of start-up, four splits of ten 32-row chunks and a slab write, and the ten
@@ -1282,26 +1115,20 @@ extern "C" int tpgsr_conv_wgrad_batch_prepare(const tpgsr_wgrad_args* w, tpgsr_w
   const tpgsr_conv_args* a = &w->c;
   const long long M = (long long)a->N * a->OH * a->OW;
   const int K = a->KH * a->KW * a->Cin;
-  const bool vecY = !w->dy_ps && (w->dy_ld & 3) == 0 && (w->dy_coff & 3) == 0 && w->dy_ld >= ((a->Cout + 3) & ~3) + w->dy_coff &&
-                    ((uintptr_t)w->dy & 15) == 0;
-  if (!(a->terms >= 1 && a->terms <= 3 && a->KH * a->KW == 1 && (a->Cin & 3) == 0 && vecY && M < (1ll << 31) &&
+  const tpgsr_wgrad_route_t r = conv_wgrad_route(w, M);
+  // (a three-k-block launch joins a batch as well: the batch kernel runs the tile loop's body, which computes the same slabs)
+  if (!((r.kernel == TPGSR_WGRAD_XBF_TILE || r.kernel == TPGSR_WGRAD_XBF_3K) && a->terms <= 3 && a->KH * a->KW == 1 && r.vecY && M < (1ll << 31) &&
         M * w->dy_ld * 4 <= 0x7fffffffll && a->wt_bf_cin == 0 && !w->dy_bf)) {
     tpgsr_set_error("tpgsr_conv_wgrad_batch_prepare: not a tile-loop split-bf16 launch");
     return TPGSR_ERR_ARG;
   }
-  int Z, MB;
-  tpgsr_wgrad_plan_host(M, K, a->Cout, &Z, &MB);
-  if (w->zsplits > 0) {
-    Z = w->zsplits;
-    MB = cdiv(cdiv(M, 64), Z) * 64;
-  }
   item->w = *w;
   item->M = (int)M;
   item->K = K;
-  item->MB = MB;
+  item->MB = r.MB;
   item->blk0 = 0;
-  item->nblk = cdiv(K, WK) * cdiv(a->Cout, BN) * Z;
-  return tpgsr_loader_bits(a);
+  item->nblk = cdiv(K, WK) * cdiv(a->Cout, BN) * r.Z;
+  return r.ld;
 }
 
 extern "C" int tpgsr_conv_wgrad_batch(const tpgsr_wgrad_batch_item* items_dev, int n, int total_blocks, int ld, int terms, void* stream) {
@@ -1316,20 +1143,16 @@ extern "C" int tpgsr_conv_wgrad_batch(const tpgsr_wgrad_batch_item* items_dev, i
     break;
   switch (ld) {
     XBF_WGB_CASE(0) XBF_WGB_CASE(1) XBF_WGB_CASE(3)
-    default:
-      tpgsr_set_error("tpgsr_conv_wgrad_batch: unsupported loader combination %d", ld);
-      return TPGSR_ERR_ARG;
+    default: return unsupported_ld("tpgsr_conv_wgrad_batch", ld);
   }
 #undef XBF_WGB_CASE
   TPGSR_LAUNCH_CHECK("tpgsr_conv_wgrad_batch");
 }
 
-extern "C" int tpgsr_conv_wgrad_xbf_launch(const tpgsr_wgrad_args* w, long long M, int K, int Z, int MB, int ld, hipStream_t st) {
+int conv_wgrad_xbf_launch(const tpgsr_wgrad_args* w, long long M, int K, const tpgsr_wgrad_route_t& r, hipStream_t st) {
   const tpgsr_conv_args* a = &w->c;
-  const int T = a->terms;
-  // three k-blocks per workgroup where the shape allows: K a multiple of 192, the plain / affine loader, dense dy, a plain stride-1 geometry
-  if (g_wg3_on && T >= 1 && T <= 2 && K % (3 * WK) == 0 && (ld == 0 || ld == 1) && !w->dy_ps && a->in_dil_w <= 1 && a->stride_w <= 1 &&
-      !a->in_ps && (a->Cin & 3) == 0 && M * (long long)w->dy_ld * 4 <= 0x7fffffffll) {
+  const int T = a->terms, ld = r.ld, Z = r.Z, MB = r.MB;
+  if (r.kernel == TPGSR_WGRAD_XBF_3K) {   // three k-blocks per workgroup (K a multiple of 192, plain / affine loader, terms 1 or 2)
     dim3 grid3((K / (3 * WK)) * cdiv(a->Cout, BN) * Z);
     if (ld == 0) {
       if (T == 1) hipLaunchKernelGGL((conv_wgrad_xbf3_kernel<0, 1>), grid3, dim3(256), 0, st, *w, (int)M, K, MB);
@@ -1349,9 +1172,7 @@ extern "C" int tpgsr_conv_wgrad_xbf_launch(const tpgsr_wgrad_args* w, long long 
     break;
   switch (ld) {
     XBF_WG_CASE(0) XBF_WG_CASE(1) XBF_WG_CASE(2) XBF_WG_CASE(3) XBF_WG_CASE(4) XBF_WG_CASE(5) XBF_WG_CASE(7) XBF_WG_CASE(17)
-    default:
-      tpgsr_set_error("tpgsr_conv_wgrad: unsupported loader combination %d", ld);
-      return TPGSR_ERR_ARG;
+    default: return unsupported_ld("tpgsr_conv_wgrad", ld);
   }
 #undef XBF_WG_CASE
   TPGSR_LAUNCH_CHECK("tpgsr_conv_wgrad(bf16 MFMA)");
@@ -1684,52 +1505,18 @@ __global__ __launch_bounds__(768, 3) void conv_wgrad_halo_kernel(tpgsr_wgrad_arg
   }
 }
 
-// geometry test shared by the plan and the launcher
-static bool wgrad_halo_shape_ok(const tpgsr_conv_args* a, int* Lcap_out) {
-  const int taps = a->KH * a->KW;
-  // only where it pays (TPGSR_XBF_WGRAD_HALO_MINWORK overrides the Cin x Cout threshold): measured at batch 48, the recognizer's
-  // 128..512-channel convolutions and the 64->256 upsample convolution gain 15-30 % over the tile loop (conv5 225 -> 157 us,
-  // upsample 156 -> 121 us) while the 64->64 trunk and 64->128 convolutions lose (42 -> 45 us: two channel blocks x 128 pixel
-  // splits, every workgroup writes a slab for six tiles of work, plus the dy pre-split) and the whole C3 step came out 1 % slower
-  // with them on -- profiles/r02b_wgrad_halo.md
-  static const long long minwork = [] { const char* e = getenv("TPGSR_XBF_WGRAD_HALO_MINWORK"); return e ? atoll(e) : 16384ll; }();
-  if ((long long)a->Cin * a->Cout < minwork) return false;
-  if (taps < 2 || taps > 12 || (a->Cin & 31) || a->stride_w > 1 || a->in_dil_w > 1 || a->in_ps || a->in_b || a->OW + a->KW - 1 < 8) return false;
-  const int Lcap = halo_capacity(a);
-  if (Lcap > 32 * 9) return false;
-  *Lcap_out = Lcap;
-  return true;
-}
-
 extern "C" int tpgsr_wgrad_halo_plan(const tpgsr_conv_args* a, int* zsplits, long long* dy_bf_bytes) {
-  static const bool on = [] { const char* e = getenv("TPGSR_XBF_WGRAD_HALO"); return !(e && e[0] == '0'); }();
-  int Lcap = 0;
-  if (!on || !a || a->terms <= 0 || !wgrad_halo_shape_ok(a, &Lcap)) return 0;
-  const long long M = (long long)a->N * a->OH * a->OW;
-  const int tiles = (int)cdiv(M, 64);
-  int cus = 256, dev = 0;
+  if (!a) return 0;
+  int cus = 256, dev = 0;      // (no device: the MI355X's count)
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   if (cus < 1) cus = 256;
-  const int groups = (a->Cin >> 5) * cdiv(a->Cout, 64);
-  int Z = cus / groups;                                   // one workgroup per CU
-  if (Z < 1) Z = 1;
-  if (Z > tiles) Z = tiles;
-  const int tpz = cdiv(tiles, Z);
-  Z = cdiv(tiles, tpz);
-  if (zsplits) *zsplits = Z;
-  if (dy_bf_bytes) *dy_bf_bytes = 3ll * cdiv(M, 16) * cdiv(a->Cout, 32) * 1024;
-  return 1;
+  return wgrad_halo_plan(a, cus, zsplits, dy_bf_bytes);
 }
 
-// returns 1 when launched, 0 when not this kernel's case, < 0 on error
-extern "C" int tpgsr_conv_wgrad_halo_launch(const tpgsr_wgrad_args* w, long long M, int ld, hipStream_t st) {
+int conv_wgrad_halo_launch(const tpgsr_wgrad_args* w, long long M, const tpgsr_wgrad_route_t& r, hipStream_t st) {
   const tpgsr_conv_args* a = &w->c;
-  const int T = a->terms;
-  int Lcap = 0;
-  if (w->zsplits <= 0 || !w->dy_bf || T <= 0 || (ld & ~7) || ld == 6 || !wgrad_halo_shape_ok(a, &Lcap)) return 0;
-  static const bool on = [] { const char* e = getenv("TPGSR_XBF_WGRAD_HALO"); return !(e && e[0] == '0'); }();
-  const size_t lds = (size_t)2 * T * Lcap * 64 + 512;
-  if (!on || lds > 150 * 1024) return 0;
+  const int T = a->terms, ld = r.ld, Lcap = r.lcap;
+  const size_t lds = r.lds_bytes;
   const int MB16 = (int)cdiv(M, 16), NB32 = cdiv(a->Cout, 32);
   {
     dim3 g((unsigned)cdiv((long long)MB16 * NB32, 4));
@@ -1743,7 +1530,7 @@ extern "C" int tpgsr_conv_wgrad_halo_launch(const tpgsr_wgrad_args* w, long long
       hipLaunchKernelGGL(dy_split_kernel<3>, g, dim3(256), 0, st, w->dy, w->dy_ld, w->dy_coff, w->dy_ps, (int)M, a->Cout, a->OH, a->OW,
                          (unsigned short*)w->dy_bf, MB16, NB32);
   }
-  const bool small = Lcap <= 32 * 7;
+  const bool small = r.ne == 7;
   const void* fn = nullptr;
 #define XBF_WGH_CASE(B)                                                                                                          \
   case B:                                                                                                                        \
@@ -1753,29 +1540,11 @@ extern "C" int tpgsr_conv_wgrad_halo_launch(const tpgsr_wgrad_args* w, long long
     break;
   switch (ld) {
     XBF_HALO_LD_CASES(XBF_WGH_CASE)
-    default: return 0;
+    default: return unsupported_ld("tpgsr_conv_wgrad", ld);
   }
 #undef XBF_WGH_CASE
-  if (lds > 64 * 1024) {
-    static std::mutex mu;
-    static std::vector<std::pair<std::pair<const void*, int>, size_t>> done;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-      tpgsr_set_error("tpgsr_conv_wgrad: hipGetDevice failed");
-      return TPGSR_ERR_LAUNCH;
-    }
-    std::lock_guard<std::mutex> lock(mu);
-    size_t* cur = nullptr;
-    for (auto& d : done)
-      if (d.first.first == fn && d.first.second == dev) cur = &d.second;
-    if (!cur || *cur < lds) {
-      if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        tpgsr_set_error("tpgsr_conv_wgrad: LDS opt-in (%zu bytes) for the halo kernel failed", lds);
-        return TPGSR_ERR_LAUNCH;
-      }
-      if (cur) *cur = lds; else done.push_back({{fn, dev}, lds});
-    }
-  }
+  const int rc = lds_opt_in(fn, lds, "tpgsr_conv_wgrad(halo)");
+  if (rc) return rc;
   const int Z = w->zsplits;
   dim3 grid((unsigned)((a->Cin >> 5) * cdiv(a->Cout, 64) * Z));
   int Mi = (int)M, Lc = Lcap, Zi = Z;
@@ -1787,7 +1556,7 @@ extern "C" int tpgsr_conv_wgrad_halo_launch(const tpgsr_wgrad_args* w, long long
     tpgsr_set_error("tpgsr_conv_wgrad(halo): launch failed: %s", hipGetErrorString(hipGetLastError()));
     return TPGSR_ERR_LAUNCH;
   }
-  return 1;
+  TPGSR_LAUNCH_CHECK("tpgsr_conv_wgrad(bf16 MFMA, halo)");
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // conv_panel.hip: the row-panel kernel of the 1x1 convolutions): operand splitting, the term-pair MFMA sequence and the forward epilogue.
 #pragma once
 #include "conv_loader.h"
+#include "conv_launch.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));

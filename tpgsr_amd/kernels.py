@@ -669,6 +669,19 @@ def make_conv_args(g: ConvGeom, inp, wt=None, out=None, *, bias=None, in2=None, 
     return a
 
 
+def conv_route(args):
+    """the kernel tpgsr_conv_fwd (ConvArgs) / tpgsr_conv_wgrad (WgradArgs) runs for `args` under the current switches, and what its launcher
+    decides on the host: (kernel name, _lib.ConvRoute / _lib.WgradRoute).  Host only -- no device needed."""
+    if isinstance(args, WgradArgs):
+        r, names, fn = _lib.WgradRoute(), _lib.WGRAD_KERNELS, _lib.load().tpgsr_conv_wgrad_route
+    else:
+        r, names, fn = _lib.ConvRoute(), _lib.CONV_KERNELS, _lib.load().tpgsr_conv_route
+    k = fn(C.byref(args), C.byref(r))
+    if k < 0:
+        raise ValueError("conv_route: a dimension of the argument block is not positive")
+    return names[k], r
+
+
 def conv_in2_scale_ok(a: ConvArgs) -> bool:
     """will tpgsr_conv_fwd take this launch with its scaled residual operand (in2_scale)?  Only the whole-CU halo kernel's loader has it"""
     return bool(_lib.load().tpgsr_conv_in2_scale_ok(C.byref(a)))
