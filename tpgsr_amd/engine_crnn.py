@@ -84,7 +84,18 @@ class PaddedLinear:
 
 
 class LstmLayer:
-    """BidirectionalLSTM (crnn.py:5-26): nn.LSTM(nIn, Hh, bidirectional) + Linear(2*Hh, nOut)."""
+    """BidirectionalLSTM (crnn.py:5-26): nn.LSTM(nIn, Hh, bidirectional) + Linear(2*Hh, nOut).
+
+    Batch limit: N <= MAX_BATCH = 64 sequences.  The persistent recurrences (csrc/lstm_seq.hip) hold two 32-row blocks, and the per-step
+    form's tpgsr_lstm_rec_gemm (csrc/crnn.hip) has no row dimension in its grid and rejects Nrows > 64; fwd / bwd raise a ValueError for a
+    larger batch instead of recording a launch that fails when the plan runs (CRNNEngine.forward checks before it records anything)."""
+    MAX_BATCH = 64
+
+    @classmethod
+    def check_batch(cls, N):
+        if N > cls.MAX_BATCH:
+            raise ValueError(f"the BiLSTM recurrence kernels take a batch of at most {cls.MAX_BATCH} sequences (batch <= {cls.MAX_BATCH}), got {N}: "
+                             "split the batch")
 
     def __init__(self, eng, prefix: str):
         self.eng, self.prefix = eng, prefix
@@ -112,8 +123,9 @@ class LstmLayer:
     def fwd(self, N, T, x, G, gh, Cst, out, e, **loader):
         """x [N][T][Cin] -> G (gates) -> out [N][T][2Hh] -> e = Linear(out) [N][T][nOut]"""
         Hh, G4, P = self.Hh, 4 * self.Hh, self.eng.P
+        self.check_batch(N)
         K.conv_fwd(K.make_conv_args(ConvGeom(N, 1, T, self.Cin, 2 * G4), x, self.wih_f, G, bias=self.bih, **loader))
-        if K.LSTM_SEQ and Hh == 256 and N <= 64 and K.lstm_seq_coresident(self.eng.device):      # the whole recurrence as one persistent launch
+        if K.LSTM_SEQ and Hh == 256 and K.lstm_seq_coresident(self.eng.device):      # the whole recurrence as one persistent launch
             if not hasattr(self, "_seq"):
                 self._seq = {}
             gran = K.LSTM_GRANULE and T <= 31
@@ -140,13 +152,14 @@ class LstmLayer:
         BatchNorm dx is the incoming gradient of"""
         eng, P, Gd, r = self.eng, self.eng.P, self.eng.G, self.r
         Hh, G4 = self.Hh, 4 * self.Hh
+        self.check_batch(N)
         # (only with deferred slab reduces: every launch then has slab buffers of its own -- the five run concurrently)
         batch = K.LSTM_WGRAD_BATCH and K.CONV_TERMS > 0 and K.deferring() and isinstance(self.emb, (ConvLayer, PaddedLinear))
         if not batch:
             self.emb.wgrad(N, 1, T, out, de)
         self.emb.dgrad(N, 1, T, de, dout)
         S = G4 // (32 * K.LSTM_BWD_KCHUNKS)                 # K-split of the recurrent gradient GEMM (K = 4 Hh)
-        seq = K.LSTM_SEQ_BWD and Hh == 256 and N <= 64 and K.lstm_seq_coresident(self.eng.device)
+        seq = K.LSTM_SEQ_BWD and Hh == 256 and K.lstm_seq_coresident(self.eng.device)
         if seq:                                              # the whole BPTT recurrence as one persistent launch
             if not hasattr(self, "_seqb"):
                 self._seqb = {}
@@ -165,36 +178,39 @@ class LstmLayer:
             # launch (tpgsr_conv_wgrad_batch; the input side of the first layer, behind the CNN's BatchNorm + ReLU loader, as a second):
             # alone each is 25-65 us of start-up, and the ten of the two layers sit at the very end of the training step
             wargs, reduces = [], []
+
+            def one(g_, cargs, dy, dw_, db_, **dy_kw):
+                # a batched launch is followed by all of its reduces; a single one by its own reduce BEFORE the next launch is set up:
+                # without deferred reduces the slab buffers are one stream-ordered scratch, which the next launch overwrites
+                Z = K.wgrad_splits(g_.M, g_.K, g_.Cout)
+                part, dbp = eng.wgrad_buffers(Z * g_.K * g_.Cout, Z * g_.Cout)
+                w_ = K.make_wgrad_args(cargs, dy, part, dbp, **dy_kw)
+                if batch:
+                    wargs.append(w_)
+                    reduces.append((part, dbp, Z, g_, dw_, db_))
+                else:
+                    K.conv_wgrad(w_)
+                    K.wgrad_reduce(part, dbp, Z, g_, dw_, db_, accumulate=True)
+
             if batch:
                 emb = self.emb
                 ge = ConvGeom(N, 1, T, emb.Cin, emb.Cout)
-                Z = K.wgrad_splits(ge.M, ge.K, ge.Cout)
-                part, dbp = eng.wgrad_buffers(Z * ge.K * ge.Cout, Z * ge.Cout)
-                dy_kw = dict(dy_ld=emb.Cp) if isinstance(emb, PaddedLinear) else {}
-                wargs.append(K.make_wgrad_args(K.make_conv_args(ge, out), de, part, dbp, **dy_kw))
-                reduces.append((part, dbp, Z, ge, Gd[emb.wname], Gd[emb.bname]))
+                one(ge, K.make_conv_args(ge, out), de, Gd[emb.wname], Gd[emb.bname],
+                    **(dict(dy_ld=emb.Cp) if isinstance(emb, PaddedLinear) else {}))
             for d, suf in enumerate(("", "_reverse")):
                 sgn = 1 if d == 0 else -1
                 # hidden side: dW_hh[d] = dG[:, d]^T h_prev, db_hh[d] = colsum(dG[:, d])
                 gh_ = ConvGeom(N, 1, T, Hh, G4, 1, 1, 0, sgn, 1, T)
-                Z = K.wgrad_splits(gh_.M, gh_.K, G4)
-                part, dbp = eng.wgrad_buffers(Z * Hh * G4, Z * G4)
-                wargs.append(K.make_wgrad_args(K.make_conv_args(gh_, out, in_ld=2 * Hh, in_coff=d * Hh), G, part, dbp,
-                                               dy_ld=2 * G4, dy_coff=d * G4))
-                reduces.append((part, dbp, Z, gh_, Gd[r + "weight_hh_l0" + suf], Gd[r + "bias_hh_l0" + suf]))
+                one(gh_, K.make_conv_args(gh_, out, in_ld=2 * Hh, in_coff=d * Hh), G, Gd[r + "weight_hh_l0" + suf], Gd[r + "bias_hh_l0" + suf],
+                    dy_ld=2 * G4, dy_coff=d * G4)
                 # input side
                 gi_ = ConvGeom(N, 1, T, self.Cin, G4)
-                Z = K.wgrad_splits(gi_.M, gi_.K, G4)
-                part, dbp = eng.wgrad_buffers(Z * self.Cin * G4, Z * G4)
-                wargs.append(K.make_wgrad_args(K.make_conv_args(gi_, x, **loader), G, part, dbp, dy_ld=2 * G4, dy_coff=d * G4))
-                reduces.append((part, dbp, Z, gi_, Gd[r + "weight_ih_l0" + suf], Gd[r + "bias_ih_l0" + suf]))
+                one(gi_, K.make_conv_args(gi_, x, **loader), G, Gd[r + "weight_ih_l0" + suf], Gd[r + "bias_ih_l0" + suf],
+                    dy_ld=2 * G4, dy_coff=d * G4)
             if batch:
                 K.conv_wgrad_batch(wargs)
-            else:
-                for w_ in wargs:
-                    K.conv_wgrad(w_)
-            for part, dbp, Z, g_, dw_, db_ in reduces:
-                K.wgrad_reduce(part, dbp, Z, g_, dw_, db_, accumulate=True)
+                for part, dbp, Z, g_, dw_, db_ in reduces:
+                    K.wgrad_reduce(part, dbp, Z, g_, dw_, db_, accumulate=True)
         if dx is not None:
             K.conv_fwd(K.make_conv_args(ConvGeom(N, 1, T, 2 * G4, self.Cin), G, self.wih_d, dx, bnb=dx_bnb))
 
@@ -405,7 +421,7 @@ class CRNNEngine(_EngineBase):
 
     # ---- execution ----------------------------------------------------------------------------------------------
     def forward(self, gray: torch.Tensor, training: bool, slot: int = 0, late_stream=None, after_late=None) -> torch.Tensor:
-        """gray (N, 1, 32, 100) -> logits [N][T][nclass] (batch-major; the module returns the (T, N, C) view).
+        """gray (N, 1, 32, 100), N <= 64 (LstmLayer.MAX_BATCH) -> logits [N][T][nclass] (batch-major; the module returns the (T, N, C) view).
         late_stream (training): the stream the operands behind conv2 are packed on, next to conv0..conv2 on the caller's stream (which
         waits for it before conv3); None: everything in order on the caller's stream.  after_late(): called once that packing is enqueued
         (or right away when there is none) -- a train step queues the SR network's prologue behind it on the same stream"""
@@ -413,6 +429,7 @@ class CRNNEngine(_EngineBase):
             raise RuntimeError("tpgsr_amd runs on the GPU only (no CPU fallback): move the module and inputs to cuda")
         if gray.dim() != 4 or gray.shape[1] != 1 or tuple(gray.shape[2:]) != self.IMG_HW:
             raise ValueError(f"CRNN expects (N, 1, {self.IMG_HW[0]}, {self.IMG_HW[1]}) input, got {tuple(gray.shape)}")
+        LstmLayer.check_batch(gray.shape[0])         # (before anything is bound, recorded or launched)
         self.bind(gray.device)
         N = gray.shape[0]
         pl = self.plans(N, training, slot)

@@ -52,6 +52,9 @@ class _CRNNFunction(torch.autograd.Function):
 
 
 class CRNN(EngineHolder, nn.Module):
+    """CRNN(32, 1, 37, 256): gray (N, 1, 32, 100) -> logits (26, N, 37).  Batch limit: N <= 64 (engine_crnn.LstmLayer.MAX_BATCH, the BiLSTM
+    recurrence kernels' row count); a larger batch raises a ValueError before anything is recorded or launched -- split it."""
+
     def __init__(self, imgH, nc, nclass, nh, n_rnn=2, leakyRelu=False):
         super().__init__()
         assert imgH % 16 == 0, "imgH has to be a multiple of 16"
