@@ -200,7 +200,8 @@ int tpgsr_conv_wgrad_route(const tpgsr_wgrad_args* w, tpgsr_wgrad_route_t* r);
 /* Several independent weight-gradient GEMMs in ONE launch (the ten of the text-prior generator's two BiLSTM layers, model/crnn/crnn.py:5-26:
  * 25-65 us each alone -- start-up, not work).  items_dev: device-resident table; an item = the arguments of one tpgsr_conv_wgrad call plus
  * what its launcher derives from them, filled on the host by tpgsr_conv_wgrad_batch_prepare (returns the loader variant `ld`, >= 0, when
- * the call is a 1x1 geometry on the split-bf16 tile-loop kernel -- the only kind a batch takes; all items of a batch share `ld` and
+ * the call is a 1x1 geometry on the split-bf16 tile-loop kernel with a loader variant the batch kernel is instantiated for (0, 1, 3) --
+ * the only kind a batch takes; all items of a batch share `ld` and
  * `terms`); blk0 = prefix sum of nblk over the preceding items, total_blocks = the full sum.  Results are those of the single launches,
  * bit for bit (same workgroups, same slabs). */
 typedef struct tpgsr_wgrad_batch_item {

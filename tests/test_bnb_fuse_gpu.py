@@ -22,10 +22,16 @@ def _act_grad64(z, act):
     return t + z * (1 - t * t) * torch.sigmoid(z)      # d/dz z tanh(softplus z)
 
 
-def _case(N, H, W, Ci, Co, KH, KW, ph, pw, act, terms, seed, in_ps=False):
+FAMILY = {"xbf_halo3": "halo", "xbf_halo": "halo", "xbf_panel": "panel", "xbf_tile": "tile"}
+
+
+def _case(N, H, W, Ci, Co, KH, KW, ph, pw, act, terms, seed, in_ps=False, family=None):
     """data-gradient-like launch dy [M][Ci] -> da [M][Co] with the BatchNorm input y [M][Co]; returns the max relative errors of
-    (da, per-block sum dz, per-block sum dz xhat) and the kernel's partial tensor"""
-    from tpgsr_amd import kernels as K
+    (da, per-block sum dz, per-block sum dz xhat) and the kernel's partial tensor.  family: the kernel family the launch must land on
+    (asserted through K.conv_route on the launched argument block; the split-K planner, which would take the small-map halo and
+    tile-loop launches, is switched off for it, and the K = 192 row panel, which is behind a switch, is switched on for "panel")"""
+    from tpgsr_amd import _lib, kernels as K
+    lib = _lib.load()
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(N, Ci, H, W, generator=g)
     w = torch.randn(Co, Ci, KH, KW, generator=g) / math.sqrt(Ci * KH * KW)
@@ -51,7 +57,19 @@ def _case(N, H, W, Ci, Co, KH, KW, ph, pw, act, terms, seed, in_ps=False):
         part = torch.full(((M + 63) // 64, 2, Co), float("nan"), device=DEV)
         keep = [y.to(DEV), mean.to(DEV), rstd.to(DEV), sc.to(DEV), sh.to(DEV)]
         bnb = dict(y=keep[0], mean=keep[1], rstd=keep[2], scale=keep[3], shift=keep[4], act=act, partial=part)
-        K.conv_fwd(K.make_conv_args(geom, xin, wf, out, in_ps=in_ps, bnb=bnb))
+        a = K.make_conv_args(geom, xin, wf, out, in_ps=in_ps, bnb=bnb)
+        if family is None:
+            K.conv_fwd(a)
+        else:
+            lib.tpgsr_splitk_set_enabled(0)
+            lib.tpgsr_panel_set_k192(1 if family == "panel" else 0)
+            try:
+                name, r = K.conv_route(a)
+                assert FAMILY.get(name) == family and r.sk_plan <= 1 and r.ld == (8 if in_ps else 0), (name, r.ld, r.sk_plan, family)
+                K.conv_fwd(a)
+            finally:
+                lib.tpgsr_splitk_set_enabled(1)
+                lib.tpgsr_panel_set_k192(0)
         torch.cuda.synchronize()
     e_out = ((out.cpu().double() - da64).abs().max() / da64.abs().max()).item()
     p = part.cpu().double()
@@ -63,27 +81,27 @@ def _case(N, H, W, Ci, Co, KH, KW, ph, pw, act, terms, seed, in_ps=False):
 TOL = {3: 3e-6, 2: 4e-5, 1: 2e-2}
 
 SHAPES = [
-    # N, H, W, Ci, Co, KH, KW, ph, pw, act            kernel family under the default routing
-    (48, 16, 64, 64, 64, 3, 3, 1, 1, "mish"),       # halo (trunk conv2 data gradient -> bn1 + mish): 768 tiles on a persistent grid
-    (48, 16, 64, 192, 64, 1, 1, 0, 0, "none"),      # row panel (GruBlock projection data gradient -> bn2)
-    (5, 8, 25, 128, 96, 3, 3, 1, 1, "relu"),        # halo, tiles spanning rows and images, Cout not a multiple of 64 (recognizer)
-    (3, 5, 13, 192, 64, 1, 1, 0, 0, "none"),        # tile loop (195 pixels: below the panel threshold), ragged last row block
-    (3, 5, 13, 64, 40, 3, 3, 1, 1, "mish"),         # halo, ragged M and ragged Cout
-    (2, 16, 50, 128, 64, 3, 3, 1, 1, "relu"),       # tile loop (halo of 278 entries: the halo kernel declines), recognizer conv1 gradient
+    # N, H, W, Ci, Co, KH, KW, ph, pw, act, kernel family (asserted in _case; the split-K planner off, the K = 192 panel on)
+    (48, 16, 64, 64, 64, 3, 3, 1, 1, "mish", "halo"),     # trunk conv2 data gradient -> bn1 + mish: 768 tiles on a persistent grid (whole-CU kernel at T <= 2)
+    (48, 16, 64, 192, 64, 1, 1, 0, 0, "none", "panel"),   # row panel (GruBlock projection data gradient -> bn2)
+    (5, 8, 25, 128, 96, 3, 3, 1, 1, "relu", "halo"),      # tiles spanning rows and images, Cout not a multiple of 64 (recognizer)
+    (3, 5, 13, 192, 64, 1, 1, 0, 0, "none", "tile"),      # tile loop (195 pixels: below the panel threshold), ragged last row block
+    (3, 5, 13, 64, 40, 3, 3, 1, 1, "mish", "halo"),       # ragged M and ragged Cout
+    (2, 16, 50, 128, 64, 3, 3, 1, 1, "relu", "tile"),     # tile loop (halo of 278 entries: the halo kernel declines), recognizer conv1 gradient
 ]
 
 
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("terms", [3, 2, 1])
 def test_bnb_epilogue_vs_fp64(shape, terms):
-    e_out, e_s, e_sx, _ = _case(*shape, terms=terms, seed=13)
+    e_out, e_s, e_sx, _ = _case(*shape[:-1], terms=terms, seed=13, family=shape[-1])
     print(f"bnb {shape} T={terms}: da {e_out:.2e}  sum dz {e_s:.2e}  sum dz xhat {e_sx:.2e}")
     assert e_out < TOL[terms] and e_s < 8 * TOL[terms] and e_sx < 8 * TOL[terms]
 
 
 def test_bnb_epilogue_unshuffle_gather():
     """data gradient of the upsample convolution (256 -> 64 through the un-PixelShuffle gather, LD 8) -> bn7, no activation"""
-    e_out, e_s, e_sx, _ = _case(6, 16, 64, 256, 64, 3, 3, 1, 1, "none", terms=2, seed=3, in_ps=True)
+    e_out, e_s, e_sx, _ = _case(6, 16, 64, 256, 64, 3, 3, 1, 1, "none", terms=2, seed=3, in_ps=True, family="halo")
     print(f"bnb un-PixelShuffle: da {e_out:.2e}  sum dz {e_s:.2e}  sum dz xhat {e_sx:.2e}")
     assert e_out < TOL[2] and e_s < 8 * TOL[2] and e_sx < 8 * TOL[2]
 

@@ -104,6 +104,8 @@ static constexpr unsigned long long kXbfFwdLd = ld_set({0, 1, 2, 3, 4, 5, 7, 8, 
 static constexpr unsigned long long kHaloLd = ld_set({0, 1, 2, 3, 4, 5, 7});               // XBF_HALO_LD_CASES (the forward kernel adds 8)
 static constexpr unsigned long long kHalo3Ld = ld_set({0, 1, 2, 3, 4, 5, 7, 37});          // H3_LD_CASES
 static constexpr unsigned long long kPanelLd = ld_set({0, 1, 4, 17});                      // PANEL_LD_CASES
+static constexpr unsigned long long kWgradBatchLd = ld_set({0, 1, 3});                     // XBF_WGB_CASE (tpgsr_conv_wgrad_batch)
+bool wgrad_batch_has_ld(int ld) { return ld_in(ld, kWgradBatchLd); }
 
 // ---- forward / data gradient ----
 // whole-CU halo kernel: the halo capacity when the launch is its own, else 0

@@ -58,4 +58,6 @@ tpgsr_conv_route_t conv_fwd_route(const tpgsr_conv_args* a, long long M);
 tpgsr_conv_route_t conv_fwd_plan_route(const tpgsr_conv_args* a, long long M, int ld);
 // halo, three-k-block, tile loop (split-bf16); tile loop, scalar loader (fp32)
 tpgsr_wgrad_route_t conv_wgrad_route(const tpgsr_wgrad_args* w, long long M);
+// the loader variants the batched weight-gradient kernel is instantiated for (a launch with another one goes out singly)
+bool wgrad_batch_has_ld(int ld);
 #pragma GCC visibility pop

@@ -1118,8 +1118,8 @@ extern "C" int tpgsr_conv_wgrad_batch_prepare(const tpgsr_wgrad_args* w, tpgsr_w
   const tpgsr_wgrad_route_t r = conv_wgrad_route(w, M);
   // (a three-k-block launch joins a batch as well: the batch kernel runs the tile loop's body, which computes the same slabs)
   if (!((r.kernel == TPGSR_WGRAD_XBF_TILE || r.kernel == TPGSR_WGRAD_XBF_3K) && a->terms <= 3 && a->KH * a->KW == 1 && r.vecY && M < (1ll << 31) &&
-        M * w->dy_ld * 4 <= 0x7fffffffll && a->wt_bf_cin == 0 && !w->dy_bf)) {
-    tpgsr_set_error("tpgsr_conv_wgrad_batch_prepare: not a tile-loop split-bf16 launch");
+        M * w->dy_ld * 4 <= 0x7fffffffll && a->wt_bf_cin == 0 && !w->dy_bf && wgrad_batch_has_ld(r.ld))) {
+    tpgsr_set_error("tpgsr_conv_wgrad_batch_prepare: not a tile-loop split-bf16 launch with a loader variant the batch kernel has");
     return TPGSR_ERR_ARG;
   }
   item->w = *w;
