@@ -323,6 +323,10 @@ int tpgsr_split_bf_program(const tpgsr_split_desc* descs_dev, int ndesc, int tot
  * (F.interpolate(mode='bicubic'), align_corners False; interfaces/base.py:852-858 with scale 2, shift -1) */
 int tpgsr_bicubic_resize(const float* in_nchw, int N, int Ctot, int C, int H, int W, int OH, int OW, float scale, float shift,
                          float* out_nhwc, void* stream);
+/* `--arch bicubic` (model/bicubic.py:11-13): out[n][c] = F.interpolate(in[n][c], scale_factor=scale, mode='bicubic', align_corners=True)
+ * for the first C of Ctot NCHW planes, NCHW out (N, C, H * scale, W * scale).  A = -0.75, source coordinate o * (in - 1) / (out - 1)
+ * (0 when out == 1), taps clamped to the border.  Integer scale >= 1; no backward (nothing trains through it). */
+int tpgsr_bicubic_upsample(const float* in_nchw, int N, int Ctot, int C, int H, int W, int scale, float* out_nchw, void* stream);
 /* AttentionUnit + context (attention_recognition_head.py:196-218, :258-260): xproj [N][T][A], sproj [N][A], wv [A], bv [1], x [N][T][D]
  * -> alpha [N][T], context [N][D] */
 int tpgsr_aster_attention(const float* xproj, const float* sproj, const float* wv, const float* bv, const float* x, int N, int T, int A,

@@ -64,6 +64,103 @@ extern "C" int tpgsr_bicubic_resize(const float* in_nchw, int N, int Ctot, int C
 }
 
 // ------------------------------------------------------------------------------------------------------
+// `--arch bicubic` (model/bicubic.py): F.interpolate(x, scale_factor=s, mode='bicubic', align_corners=True) of the first C of Ctot
+// NCHW planes, NCHW out.  One thread = BU_PX adjacent output pixels of one output row, for every channel: the column tap indices and
+// their four weight quadruples are computed once and reused by all C planes and tap rows (the row's index and weight are re-derived
+// per row from the row fraction: a few operations, against 64 live tap addresses); a thread's pixels go out as one 16-byte store where the row
+// length and the pointer allow it (consecutive threads = consecutive 16-byte pieces of a row), scalar stores at ragged row ends.
+// The source coordinate o * (in - 1) / (out - 1) is formed in integers (quotient = first tap, remainder / (out - 1) = fraction), so
+// the fraction carries one rounding instead of the cancellation of floor() on a float product.
+// ------------------------------------------------------------------------------------------------------
+#define BU_PX 4
+__device__ __forceinline__ float bu_src(int o, int in_size, int out_size, int& i0) {      // -> the tap fraction
+  if (out_size <= 1) {
+    i0 = 0;
+    return 0.f;
+  }
+  const long long num = (long long)o * (in_size - 1);
+  const int den = out_size - 1;
+  i0 = (int)(num / den);
+  return (float)(num - (long long)i0 * den) / (float)den;
+}
+__device__ __forceinline__ float bu_weight(float t, int a) {      // element a of aster_cubic(t, .)
+  const float A = -0.75f;
+  if (a == 1 || a == 2) {
+    const float x = a == 1 ? t : 1.f - t;
+    return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+  }
+  const float x = a == 0 ? t + 1.f : 2.f - t;
+  return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
+}
+
+__global__ __launch_bounds__(256) void bicubic_upsample_kernel(const float* __restrict__ in, int N, int Ctot, int C, int H, int W, int OH,
+                                                               int OW, float* __restrict__ out) {
+  const int groups = (OW + BU_PX - 1) / BU_PX;
+  const long long total = (long long)N * OH * groups;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int gx = (int)(i % groups);
+  const long long r = i / groups;
+  const int oh = (int)(r % OH), n = (int)(r / OH);
+  const int ow0 = gx * BU_PX;
+  int y0, xi[BU_PX][4];
+  float wx[BU_PX][4];
+  const float ty = bu_src(oh, H, OH, y0);
+#pragma unroll
+  for (int p = 0; p < BU_PX; ++p) {
+    int x0;
+    aster_cubic(bu_src(min(ow0 + p, OW - 1), W, OW, x0), wx[p]);      // (a pixel past the row end repeats the last one and is not stored)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) xi[p][b] = aster_clamp(x0 - 1 + b, W - 1);
+  }
+  const bool vec = (OW % BU_PX) == 0;
+  for (int c = 0; c < C; ++c) {
+    const float* src = in + ((size_t)n * Ctot + c) * H * W;
+    float acc[BU_PX];
+#pragma unroll
+    for (int p = 0; p < BU_PX; ++p) acc[p] = 0.f;
+    // one tap row at a time: unrolled over the rows (and planes) the compiler keeps all 64 tap addresses of a thread live as 64-bit
+    // pairs -- 228 VGPRs, two waves per SIMD; the row's weight and clamped index are a handful of wave-uniform-cost operations
+#pragma unroll 1
+    for (int a = 0; a < 4; ++a) {
+      const float* row = src + (size_t)aster_clamp(y0 - 1 + a, H - 1) * W;
+      const float wya = bu_weight(ty, a);
+#pragma unroll
+      for (int p = 0; p < BU_PX; ++p) {
+        float rowv = 0.f;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) rowv += row[xi[p][b]] * wx[p][b];
+        acc[p] += rowv * wya;
+      }
+    }
+    float* dst = out + (((size_t)n * C + c) * OH + oh) * OW + ow0;
+    if (vec && (((uintptr_t)dst) & 15) == 0) {
+      *reinterpret_cast<floatx4*>(dst) = floatx4{acc[0], acc[1], acc[2], acc[3]};
+    } else {
+#pragma unroll
+      for (int p = 0; p < BU_PX; ++p)
+        if (ow0 + p < OW) dst[p] = acc[p];
+    }
+  }
+}
+
+extern "C" int tpgsr_bicubic_upsample(const float* in_nchw, int N, int Ctot, int C, int H, int W, int scale, float* out_nchw, void* stream) {
+  TPGSR_CHECK_ARG(in_nchw && out_nchw, "tpgsr_bicubic_upsample: null pointer");
+  TPGSR_CHECK_ARG(N > 0 && H > 0 && W > 0, "tpgsr_bicubic_upsample: N, H and W must be at least 1 (got N %d, H %d, W %d)", N, H, W);
+  TPGSR_CHECK_ARG(C >= 1 && C <= Ctot, "tpgsr_bicubic_upsample: reads the first C of Ctot planes, 1 <= C <= Ctot (got C %d, Ctot %d)", C, Ctot);
+  TPGSR_CHECK_ARG(scale >= 1, "tpgsr_bicubic_upsample: the integer scale factor must be at least 1 (got %d)", scale);
+  TPGSR_CHECK_ARG((long long)H * scale <= 0x7fffffffLL && (long long)W * scale <= 0x7fffffffLL,
+                  "tpgsr_bicubic_upsample: H * scale and W * scale must stay below 2^31 (got H %d, W %d, scale %d)", H, W, scale);
+  const int OH = H * scale, OW = W * scale;
+  const long long total = (long long)N * OH * ((OW + BU_PX - 1) / BU_PX);
+  TPGSR_CHECK_ARG(total <= 0x7fffffffLL * 256, "tpgsr_bicubic_upsample: N * OH * ceil(OW / %d) = %lld threads exceed the grid limit 2^31 * 256",
+                  BU_PX, total);
+  hipLaunchKernelGGL(bicubic_upsample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in_nchw, N, Ctot, C, H,
+                     W, OH, OW, out_nchw);
+  TPGSR_LAUNCH_CHECK("tpgsr_bicubic_upsample");
+}
+
+// ------------------------------------------------------------------------------------------------------
 // attention of one decoder step, one workgroup per sequence:
 //   v[t] = wv . tanh(sproj[n] + xproj[n][t]) + bv;  alpha = softmax_t(v);  context[n] = sum_t alpha[t] x[n][t]
 // ------------------------------------------------------------------------------------------------------

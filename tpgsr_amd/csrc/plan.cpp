@@ -78,6 +78,7 @@ const std::unordered_map<std::string, Entry>& registry() {
       TPGSR_REG(tpgsr_semantic_loss_fwd), TPGSR_REG(tpgsr_semantic_loss_bwd), TPGSR_REG(tpgsr_split_bf_program),
       TPGSR_REG(tpgsr_copy_strided), TPGSR_REG(tpgsr_resize_nearest_fwd), TPGSR_REG(tpgsr_resize_nearest_bwd), TPGSR_REG(tpgsr_resize_bilinear_fwd),
       TPGSR_REG(tpgsr_resize_bilinear_bwd), TPGSR_REG(tpgsr_dilate2d), TPGSR_REG(tpgsr_subsample2d), TPGSR_REG(tpgsr_hreduce), TPGSR_REG(tpgsr_hbroadcast),
+      TPGSR_REG(tpgsr_bicubic_upsample),
   };
   return r;
 }

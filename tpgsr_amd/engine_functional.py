@@ -21,7 +21,7 @@ Two ways to run it:
   `.grad` views).
 
 `FunctionalSREngine` (below) is the same adapter on the SR-network side of the protocol, for the `_TL` baseline backbones of the cascade loop
-(`TPGSR_SR_RECORD=0` switches ITS recording off)."""
+(`TPGSR_SR_RECORD=0` switches ITS recording off); `PlainSREngine` is that adapter for the prior-free baselines (SRResNet / RDN / VDSR)."""
 import os
 from typing import Dict, Optional
 
@@ -299,3 +299,92 @@ class FunctionalSREngine(FunctionalEngine):
             torch.autograd.backward(y, dsr.reshape(y.shape))
         return t.grad.contiguous()
 
+
+
+class PlainSREngine(FunctionalSREngine):
+    """`FunctionalSREngine` for a backbone WITHOUT a text prior: the reference's prior-free baselines (`--arch srres | rdn | vdsr`,
+    model/{srresnet,rdn,vdsr}.py SRResNet / RDN / VDSR), which the `else:` branch of the train loop (interfaces/super_resolution.py:409-424)
+    trains with `model(images_lr[:, :channel_num])`.  `SRTrainStep`, `FusedAdam`, `ArenaPool` and `TextSREvaluator` drive the module
+    through this adapter; `module(x)` under autograd keeps working on its own.
+
+    The same two modes: RECORDED (default, `TPGSR_SR_RECORD=0` switches it off) traces `module(lr)` once per (shape, training, slot,
+    policy) into a forward and a backward plan -- parameter gradients through `functional.GRAD_SINK` into the arena, weight gradients on
+    the weight-gradient stream with one batched slab reduce; otherwise operator by operator through autograd.  The input image needs no
+    gradient, so the first layer's data gradient is never launched, and `backward` returns nothing."""
+
+    def _trace_sr(self, shape, training):
+        dev = self.device
+        N = shape[0]
+        lr = torch.empty(*shape, device=dev)
+        fwd = Plan("sr_plain_fwd")
+        out = dict(fwd=fwd, lr=lr)
+        with recording(fwd), K.conv_terms(K.terms_for("sr", "fwd")):
+            if training:
+                with torch.enable_grad():
+                    y = self.module(lr)
+            else:
+                with torch.no_grad():
+                    y = self.module(lr)
+        assert y.is_contiguous() and y.shape[0] == N
+        out["sr"] = y.detach()
+        if not training:
+            return out
+        bwd = Plan("sr_plain_bwd")
+        bwd.overlap = os.environ.get("TPGSR_OVERLAP_WGRAD", "1") != "0"
+        bwd.deferred = [] if os.environ.get("TPGSR_DEFER_REDUCE", "1") != "0" else None
+        dsr = torch.empty_like(out["sr"])
+        self.arena.attach_grads()
+        grads = {p.data_ptr(): p.grad for p in self.module.parameters() if p.requires_grad}
+        prev, Fh.GRAD_SINK = Fh.GRAD_SINK, grads
+        try:
+            with recording(bwd), K.conv_terms(K.terms_for("sr", "bwd")):
+                torch.autograd.backward(y, dsr)
+                if bwd.deferred is not None:
+                    K.flush_wgrad_reduces()
+                K._REC.join()
+        finally:
+            Fh.GRAD_SINK = prev
+        out.update(bwd=bwd, dsr=dsr, graph=y)       # `graph` keeps the saved activations alive
+        return out
+
+    def forward(self, lr, training, prior=None, slot: int = 0, defer_join: bool = False, pre_done: bool = False) -> torch.Tensor:
+        """lr (N, C, H, W) -> SR image (N, C, 2H, 2W)"""
+        if prior is not None:
+            raise ValueError(f"{type(self.module).__name__} takes no text prior")
+        self._check_mode(training)
+        self.bind(lr.device)
+        if self.record:
+            pl = self.sr_plans(lr.shape, training, slot)
+            K.copy(lr.contiguous(), pl["lr"], lr.numel())
+            pl["fwd"].run()
+            if training:
+                self._pending_batches += 1
+                self._saved[slot] = (lr.shape[0], pl)
+            res = torch.empty_like(pl["sr"])
+            K.copy(pl["sr"], res, res.numel())
+            return res
+        with K.conv_terms(K.terms_for("sr", "fwd")):
+            if not training:
+                with torch.no_grad():
+                    return self.module(lr)
+            with torch.enable_grad():
+                y = self.module(lr.detach())
+        self._saved[slot] = (None, y)
+        return y.detach()
+
+    def backward(self, x_shape, sr, dsr, slot: int = 0, defer_join: bool = False) -> None:
+        """d loss / d SR image -> parameter gradients, accumulated into the arena (there is no prior to return a gradient for)"""
+        if slot not in self._saved:
+            raise RuntimeError(f"{type(self.module).__name__}: backward without a training-mode forward in slot {slot}")
+        if self.record:
+            n, pl = self._saved.pop(slot)
+            assert n == x_shape[0]
+            self.arena.attach_grads()                       # (same addresses as at trace time: the arena does not move)
+            K.copy(dsr.contiguous(), pl["dsr"], pl["dsr"].numel())
+            pl["bwd"].run()
+            return None
+        _, y = self._saved.pop(slot)
+        self.arena.attach_grads()
+        with K.conv_terms(K.terms_for("sr", "bwd")):
+            torch.autograd.backward(y, dsr.reshape(y.shape))
+        return None

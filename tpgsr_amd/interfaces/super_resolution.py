@@ -36,15 +36,72 @@ def _warn_hw_queues(collective: bool):
                       "(INTEGRATION.md section 4)." % os.environ.get("GPU_MAX_HW_QUEUES", "unset (HIP default 4)"), RuntimeWarning, stacklevel=3)
 
 
+IMAGE_CRITS = ("image_loss", "mse", "l1")
+
+
+def _image_crit(who: str, image_crit: str, gradient, loss_weight):
+    """the image criterion of a train step (interfaces/base.py:332-368) -> (gradient, w0, w1) of its kernels: "image_loss" =
+    ImageLoss(gradient, loss_weight) of tsrn / tsrn_tl_cascade; "mse" = nn.MSELoss() of srres / vdsr / srresnet_tl / srcnn_tl / vdsr_tl (the
+    image-loss kernels with the gradient term off and w0 = 1); "l1" = nn.L1Loss() of rdn / rdn_tl (tpgsr_l1_loss_fwd / _bwd)"""
+    if image_crit not in IMAGE_CRITS:
+        raise ValueError(f"{who}: image_crit={image_crit!r}, expected 'image_loss', 'mse' or 'l1'")
+    if image_crit != "image_loss":
+        return False, 1.0, 0.0
+    return bool(gradient), float(loss_weight[0]), float(loss_weight[1])
+
+
+def _image_crit_value(image_crit, sr, hr, N, C, H2, W2, gradient, w0, w1, part, loss):
+    """criterion(sr, hr).mean() * 100 -> the device scalar `loss` (two launches on the current stream)"""
+    if image_crit == "l1":
+        K.l1_loss_fwd(sr, hr, sr.numel(), part, _NBLK_IMG)
+    else:
+        K.image_loss_fwd(sr, hr, N, C, H2, W2, gradient, part, _NBLK_IMG)
+    n_gp = N * min(C, 3) * H2 * W2 if gradient else 0
+    K.image_loss_finalize(part, _NBLK_IMG, sr.numel(), n_gp, w0 * 100.0, w1 * 100.0, loss)
+
+
+def _image_crit_grad(image_crit, sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, dsr):
+    """d (criterion(sr, hr).mean() * dloss) / d sr -> dsr"""
+    if image_crit == "l1":
+        K.l1_loss_bwd(sr, hr, dloss, sr.numel(), w0, dsr)
+    else:
+        K.image_loss_bwd(sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, dsr)
+
+
+def _refuse_exchange_with_functional_engine(who, modules, advice):
+    from ..engine_functional import FunctionalSREngine
+    for m in modules:
+        if isinstance(m._engine(), FunctionalSREngine):
+            raise NotImplementedError(f"{who}: gradient exchange (world_size > 1 / force_collectives) with the operator-level SR "
+                                      f"backbone {type(m).__name__} is not supported: its engine has no gradient-bucket schedule "
+                                      f"(DESIGN section 7).  {advice}")
+
+
 class TSRNTrainStep:
+    """The single-network step: `--arch tsrn` (config C2) with the defaults, and the `else:` branch of the reference's train loop
+    (interfaces/super_resolution.py:409-424) for the prior-free baselines -- any module whose `_engine()` follows the SR engine protocol:
+        SRTrainStep(srresnet.SRResNet(mask=True), image_crit="mse")          # train_SRResNet.sh
+        SRTrainStep(rdn.RDN(), image_crit="l1", channels=3)                  # train_RDN.sh
+        SRTrainStep(vdsr.VDSR(), image_crit="mse", channels=3)
+    image_crit: the criterion interfaces/base.py:332-347 pairs with the architecture (`_image_crit` above).  channels: the reference's
+    channel_num -- the step feeds lr[:, :channels] and compares with hr[:, :channels] (:410-416); the prefix is gathered by a kernel
+    launch (tpgsr_copy_strided), so capture() / replay() work on it."""
+
     def __init__(self, model, gradient=True, loss_weight=(1.0, 1e-4), lr=1e-3, betas=(0.5, 0.999), max_norm=0.25,
-                 process_group=None, world_size: int = 1, force_collectives: bool = False, precision: Optional[str] = None):
+                 process_group=None, world_size: int = 1, force_collectives: bool = False, precision: Optional[str] = None,
+                 image_crit: str = "image_loss", channels: Optional[int] = None):
         self.model = model
+        self.image_crit = image_crit
+        if channels is not None and int(channels) < 1:
+            raise ValueError(f"TSRNTrainStep: channels={channels!r}, expected None or a positive plane count")
+        self.channels = None if channels is None else int(channels)
         # arithmetic policy of the step's GEMMs (kernels.py): `precision`, else an explicit TPGSR_CONV_PREC / set_conv_prec, else "x2"
         self.precision = K.train_step_policy(precision)
         self.collective = world_size > 1 or bool(force_collectives)   # force: drive RCCL at world size 1 too (tests)
         _warn_hw_queues(self.collective)
-        self.gradient, self.w0, self.w1 = bool(gradient), float(loss_weight[0]), float(loss_weight[1])
+        self.gradient, self.w0, self.w1 = _image_crit("TSRNTrainStep", image_crit, gradient, loss_weight)
+        if self.collective:
+            _refuse_exchange_with_functional_engine("TSRNTrainStep", [model], "Train the baseline backbones on one GPU per process group of size 1.")
         self.pool = ArenaPool([model])
         self.opt = FusedAdam([model], lr=lr, betas=betas, clip_modules=[model], max_norm=max_norm, pool=self.pool)
         self.pg, self.world = process_group, world_size
@@ -57,11 +114,23 @@ class TSRNTrainStep:
         dev = lr_img.device
         if self._static is None or self._static["dev"] != dev or self._static["shape"] != tuple(lr_img.shape):
             N, C, H, W = lr_img.shape
+            if self.channels is not None and self.channels > C:
+                raise ValueError(f"TSRNTrainStep: channels={self.channels} of a batch with {C} planes")
+            Cs = C if self.channels is None else self.channels
             self._static = dict(dev=dev, shape=tuple(lr_img.shape),
                                 part=torch.empty(_NBLK_IMG, 2, device=dev), loss=torch.zeros((), device=dev),
-                                dloss=torch.full((1,), 100.0, device=dev), dsr=torch.empty(N, C, 2 * H, 2 * W, device=dev),
+                                dloss=torch.full((1,), 100.0, device=dev), dsr=torch.empty(N, Cs, 2 * H, 2 * W, device=dev),
                                 inv_world=torch.full((1,), 1.0 / self.world, device=dev))
+            if Cs != C:      # the channel prefixes the network and the criterion see
+                self._static.update(lr_c=torch.empty(N, Cs, H, W, device=dev), hr_c=torch.empty(N, Cs, 2 * H, 2 * W, device=dev))
         return self._static
+
+    @staticmethod
+    def _prefix(src, dst):
+        """dst (N, Cs, H, W) = src[:, :Cs] of a contiguous NCHW batch: one strided-copy launch (rows = samples)"""
+        N, C, H, W = src.shape
+        Cs = dst.shape[1]
+        K.copy_strided(src, C * H * W, 0, dst, Cs * H * W, 0, N, Cs * H * W)
 
     def _phase_a(self, lr_img, hr_img):
         """zero_grad + forward + loss + backward (everything before the gradient exchange)"""
@@ -70,18 +139,22 @@ class TSRNTrainStep:
         st = self._buffers(lr_img)
         N, C, H, W = lr_img.shape
         self.opt.zero_grad()
+        hr = hr_img.contiguous()
+        if "lr_c" in st:
+            if tuple(hr.shape) != (N, C, 2 * H, 2 * W):
+                raise ValueError(f"TSRNTrainStep: hr is {tuple(hr.shape)}, expected {(N, C, 2 * H, 2 * W)}")
+            self._prefix(lr_img.contiguous(), st["lr_c"])
+            self._prefix(hr, st["hr_c"])
+            lr_img, hr, C = st["lr_c"], st["hr_c"], st["lr_c"].shape[1]
         sr = eng.forward(lr_img, True)
         H2, W2 = 2 * H, 2 * W
-        hr = hr_img.contiguous()
         # the loss VALUE is for the caller's log (the gradient below does not read it): its pass over sr / hr and the single-wave finalize run
         # on the auxiliary stream next to the backward pass, not in front of it
         main, aux = K.current_stream(), K.aux_stream(lr_img.device)
         K.order(aux, main)
         with K.stream_ctx(aux):
-            K.image_loss_fwd(sr, hr, N, C, H2, W2, self.gradient, st["part"], _NBLK_IMG)
-            n_gp = N * min(C, 3) * H2 * W2 if self.gradient else 0
-            K.image_loss_finalize(st["part"], _NBLK_IMG, sr.numel(), n_gp, self.w0 * 100.0, self.w1 * 100.0, st["loss"])
-        K.image_loss_bwd(sr, hr, st["dloss"], N, C, H2, W2, self.gradient, self.w0, self.w1, st["dsr"])
+            _image_crit_value(self.image_crit, sr, hr, N, C, H2, W2, self.gradient, self.w0, self.w1, st["part"], st["loss"])
+        _image_crit_grad(self.image_crit, sr, hr, st["dloss"], N, C, H2, W2, self.gradient, self.w0, self.w1, st["dsr"])
         eng.backward(tuple(lr_img.shape), sr, st["dsr"])
         K.order(main, aux)
         self.last_sr = sr
@@ -162,6 +235,9 @@ class TSRNTrainStep:
         return self._graph_loss
 
 
+SRTrainStep = TSRNTrainStep      # the name the prior-free baselines are trained under (same class)
+
+
 def parse_crnn_data(imgs_input: torch.Tensor) -> torch.Tensor:
     """TextBase.parse_crnn_data (reference interfaces/base.py:806-829): bicubic resize of the RGB channels to (32, 100)
     and luminance -> (N, 1, 32, 100).  Differentiable (later cascade stages back-propagate into the previous SR)."""
@@ -214,8 +290,7 @@ class TPGSRTrainStep:
         # the image criterion (interfaces/base.py:355-368): "image_loss" = ImageLoss(gradient, loss_weight) of tsrn / tsrn_tl_cascade;
         # "mse" = nn.MSELoss() of srresnet_tl / srcnn_tl / vdsr_tl (the image-loss kernels with the gradient term off and w0 = 1);
         # "l1" = nn.L1Loss() of rdn_tl (tpgsr_l1_loss_fwd / _bwd).  All three: .mean() * 100, value computed on the teacher's stream
-        if image_crit not in ("image_loss", "mse", "l1"):
-            raise ValueError(f"TPGSRTrainStep: image_crit={image_crit!r}, expected 'image_loss', 'mse' or 'l1'")
+        self.gradient, self.w0, self.w1 = _image_crit("TPGSRTrainStep", image_crit, gradient, loss_weight)
         self.image_crit = image_crit
         self.collective = world_size > 1 or bool(force_collectives)   # force: drive RCCL at world size 1 too (tests)
         _warn_hw_queues(self.collective)
@@ -225,16 +300,8 @@ class TPGSRTrainStep:
         if hasattr(teacher, "_engine") and all(teacher is not m for m in self.stu):
             teacher._engine().role = "teacher"      # arithmetic policy: its output is a soft target only (kernels.terms_for)
         self.stu_iter, self.sr_share, self.tpg_share = stu_iter, sr_share, tpg_share
-        self.gradient, self.w0, self.w1 = bool(gradient), float(loss_weight[0]), float(loss_weight[1])
-        if image_crit != "image_loss":
-            self.gradient, self.w0, self.w1 = False, 1.0, 0.0
         if self.collective:
-            from ..engine_functional import FunctionalSREngine
-            for m in self.sr:
-                if isinstance(m._engine(), FunctionalSREngine):
-                    raise NotImplementedError(f"TPGSRTrainStep: gradient exchange (world_size > 1 / force_collectives) with the operator-level SR "
-                                              f"backbone {type(m).__name__} is not supported: its engine has no gradient-bucket schedule "
-                                              "(DESIGN section 7).  Train the _TL baseline backbones on one GPU per process group of size 1.")
+            _refuse_exchange_with_functional_engine("TPGSRTrainStep", self.sr, "Train the _TL baseline backbones on one GPU per process group of size 1.")
         mods = self.sr + self.stu
         # one flat parameter / gradient buffer: SR net(s) first, then the students = the order their gradients become final
         self.pool = ArenaPool(mods)
@@ -365,12 +432,7 @@ class TPGSRTrainStep:
                     K.ctc_loss(logits, 26 * 37, 37, ctc[0], ctc[1], ctc[2], None, N, 26, 37, 0, 0.0, st["ctc_nll"][i], None, False, ctc[4])
                     if not K.DRYRUN:
                         st["l_sem"][i].add_((st["ctc_nll"][i] * ctc[3]).mean())
-                if self.image_crit == "l1":
-                    K.l1_loss_fwd(sr, hr, sr.numel(), st["part_img"][i], _NBLK_IMG)
-                else:
-                    K.image_loss_fwd(sr, hr, N, C, H2, W2, self.gradient, st["part_img"][i], _NBLK_IMG)
-                n_gp = N * min(C, 3) * H2 * W2 if self.gradient else 0
-                K.image_loss_finalize(st["part_img"][i], _NBLK_IMG, sr.numel(), n_gp, self.w0 * 100.0, self.w1 * 100.0, st["l_img"][i])
+                _image_crit_value(self.image_crit, sr, hr, N, C, H2, W2, self.gradient, self.w0, self.w1, st["part_img"][i], st["l_img"][i])
                 if self.ssim_loss:      # loss_img += (1 - ssim.mean()) * 10: the mean by tpgsr_ssim, the scalar arithmetic by three ATen launches
                     K.ssim(sr, hr, st["ssim_win"], 11, N, C, H2, W2, st["ssim_part"], 256, st["ssim_out"])
                     if not K.DRYRUN:
@@ -389,10 +451,7 @@ class TPGSRTrainStep:
         for i in range(self.stu_iter - 1, -1, -1):
             stu = self.stu[0 if self.tpg_share else i]
             srm = self.sr[0 if self.sr_share else i]
-            if self.image_crit == "l1":
-                K.l1_loss_bwd(srs[i], hr, st["dloss"], srs[i].numel(), self.w0, st["dsr"][i])
-            else:
-                K.image_loss_bwd(srs[i], hr, st["dloss"], N, C, H2, W2, self.gradient, self.w0, self.w1, st["dsr"][i])
+            _image_crit_grad(self.image_crit, srs[i], hr, st["dloss"], N, C, H2, W2, self.gradient, self.w0, self.w1, st["dsr"][i])
             if self.ssim_loss:             # d/d sr of (1 - mean ssim) * 10, added to the first three channels of the image-loss gradient
                 K.ssim_bwd(srs[i], hr, st["ssim_win"], 11, N, C, H2, W2, st["ssim_gm"], None, -10.0 / (N * min(C, 3) * H2 * W2), st["dsr"][i], True)
             if i < self.stu_iter - 1:      # gradient arriving through the next stage's parse_crnn_data
@@ -615,8 +674,21 @@ class TextSREvaluator:
     attention decode -- + string comparison (utils/metrics.py, utils/util.py).
     No dropout of the prior, no gradient state, no host round trip before the strings are built."""
 
-    def __init__(self, sr_models, tpg_models, recognizer=None, stu_iter=1, sr_share=True, tpg_share=False, voc_type="lower"):
+    def __init__(self, sr_models, tpg_models, recognizer=None, stu_iter=1, sr_share=True, tpg_share=False, voc_type="lower",
+                 channels: Optional[int] = None):
         self.sr = list(sr_models) if isinstance(sr_models, (list, tuple)) else [sr_models]
+        # tpg_models=None: the prior-free pass (interfaces/super_resolution.py:770-793) -- sr = sr_models[0](lr[:, :channels]) for a module
+        # with an engine (tsrn.TSRN, srresnet.SRResNet, rdn.RDN, vdsr.VDSR) or a model.bicubic.BICUBIC; no text-prior generator runs
+        self.plain = tpg_models is None
+        self.channels = None if channels is None else int(channels)
+        if self.plain:
+            if recognizer is None:
+                raise ValueError("TextSREvaluator(sr_models, None): the prior-free pass needs recognizer=")
+            if not self.sr:
+                raise ValueError("TextSREvaluator(sr_models, None): the prior-free pass needs an SR model")
+            tpg_models = []
+        elif channels is not None:
+            raise ValueError("TextSREvaluator: channels= belongs to the prior-free pass (tpg_models=None)")
         self.tpg = list(tpg_models) if isinstance(tpg_models, (list, tuple)) else [tpg_models]
         self.recognizer = recognizer if recognizer is not None else self.tpg[0]
         self.stu_iter, self.sr_share, self.tpg_share, self.voc_type = stu_iter, sr_share, tpg_share, voc_type
@@ -628,11 +700,24 @@ class TextSREvaluator:
     def super_resolve(self, images_lr):
         """-> (list of the stu_iter SR images, list of their (N, 26, 37) text priors)"""
         for m in self.sr + self.tpg:
-            if m.training:
+            if getattr(m, "training", False):
                 raise RuntimeError("TextSREvaluator needs the networks in eval() mode")
         lr = images_lr.contiguous().float()
         N, C, H, W = lr.shape
         dev = lr.device
+        if self.plain:
+            from ..model.bicubic import BICUBIC
+            srm = self.sr[0]
+            Cs = C if self.channels is None else self.channels
+            if not 1 <= Cs <= C:
+                raise ValueError(f"TextSREvaluator: channels={Cs} of a batch with {C} planes")
+            if isinstance(srm, BICUBIC):
+                return [srm(lr, channels=Cs)], []        # (the kernel reads the channel prefix itself)
+            if Cs != C:
+                lr_c = torch.empty(N, Cs, H, W, device=dev)
+                TSRNTrainStep._prefix(lr, lr_c)
+                lr = lr_c
+            return [srm._engine().forward(lr, False)], []
         cascade, ch, cw = lr, H, W
         srs, priors = [], []
         for i in range(self.stu_iter):
@@ -680,7 +765,16 @@ class TextSREvaluator:
         from ..utils.ssim_psnr import calculate_psnr
         srs, priors = self.super_resolve(images_lr)
         sr = srs[-1]
-        out = dict(images_sr=srs, priors=priors, psnr=calculate_psnr(sr, images_hr), ssim=self._ssim(sr, images_hr),
+        hr_m = images_hr
+        if sr.shape[1] != images_hr.shape[1]:
+            # prior-free pass on a channel prefix: PSNR / SSIM read the first three planes of both images (utils/ssim_psnr.py:12), so HR is
+            # cut to the SR image's plane count
+            hr = images_hr.contiguous().float()
+            if sr.shape[1] > hr.shape[1] or sr.shape[1] < min(3, hr.shape[1]):
+                raise ValueError(f"TextSREvaluator: SR image has {sr.shape[1]} planes, HR {hr.shape[1]}")
+            hr_m = torch.empty(hr.shape[0], sr.shape[1], hr.shape[2], hr.shape[3], device=hr.device)
+            TSRNTrainStep._prefix(hr, hr_m)
+        out = dict(images_sr=srs, priors=priors, psnr=calculate_psnr(sr, hr_m), ssim=self._ssim(sr, hr_m),
                    pred_sr=self.recognize(sr), pred_lr=self.recognize(images_lr), pred_hr=self.recognize(images_hr))
         if label_strs is not None:
             tgt = [str_filt(s, self.voc_type) for s in label_strs]

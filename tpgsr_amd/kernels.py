@@ -1400,6 +1400,10 @@ def bicubic_resize(x_nchw, N, Ctot, C_, H, W, OH, OW, scale, shift, out_nhwc):
     _launch("tpgsr_bicubic_resize", _p(x_nchw), N, Ctot, C_, H, W, OH, OW, float(scale), float(shift), _p(out_nhwc))
 
 
+def bicubic_upsample(x_nchw, N, Ctot, C_, H, W, scale, out_nchw):
+    _launch("tpgsr_bicubic_upsample", _p(x_nchw), N, Ctot, C_, H, W, int(scale), _p(out_nchw))
+
+
 def aster_attention(xproj, sproj, wv, bv, x, N, T, A, D, alpha, context):
     _launch("tpgsr_aster_attention", _p(xproj), _p(sproj), _p(wv), _p(bv), _p(x), N, T, A, D, _p(alpha), _p(context))
 

@@ -38,12 +38,13 @@ def spatial_text_embedding(info_gen: InfoGen, text_emb: torch.Tensor, size):
     return Fh.interpolate_bilinear(info_gen.nhwc(Fh.to_nhwc(text_emb)), size)
 
 
-def sr_engine(module):
-    """the lazily built engine adapter of a `_TL` backbone (process-local state, like nn_params.EngineHolder's `_eng`)"""
+def sr_engine(module, prior=True):
+    """the lazily built engine adapter of a `_TL` backbone, or (prior=False) of its prior-free sibling (process-local state, like
+    nn_params.EngineHolder's `_eng`)"""
     eng = module.__dict__.get("_eng")
     if eng is None:
-        from ..engine_functional import FunctionalSREngine
-        eng = FunctionalSREngine(module)
+        from ..engine_functional import FunctionalSREngine, PlainSREngine
+        eng = FunctionalSREngine(module) if prior else PlainSREngine(module)
         module.__dict__["_eng"] = eng
     return eng
 
