@@ -1,7 +1,10 @@
-"""CPU: the C-ABI shared library loads and exports every symbol include/tpgsr_hip.h declares (no kernel is launched)."""
+"""CPU: the C-ABI shared library loads and exports every symbol include/tpgsr_hip.h declares, and the ctypes binding derived from that
+header (tpgsr_amd/_abi.py, _lib.py) states what the C++ compiler reads in it (no kernel is launched)."""
 import ctypes
+import keyword
 import os
 import re
+import subprocess
 
 import pytest
 
@@ -49,7 +52,189 @@ def test_struct_layouts(lib):
     lib.tpgsr_sizeof.restype = ctypes.c_int
     for which, st in enumerate(_lib.ABI_STRUCTS):
         assert lib.tpgsr_sizeof(which) == ctypes.sizeof(st), st.__name__
-    assert len(_lib.ABI_STRUCTS) == 10 and lib.tpgsr_sizeof(len(_lib.ABI_STRUCTS)) == -1    # the list covers every struct the library knows
+    assert len(_lib.ABI_STRUCTS) == 13 and lib.tpgsr_sizeof(13) == -1    # the list covers every struct the library knows
+    assert set(_lib.ABI_STRUCTS) == set(_lib._CLASSES.values()) and set(_lib._CLASSES) == set(_lib.ABI.structs)  # ... and every struct / union the header declares
+
+
+_CXX = {ctypes.c_int: "int", ctypes.c_longlong: "long long", ctypes.c_ulonglong: "unsigned long long", ctypes.c_float: "float",
+        ctypes.c_double: "double", ctypes.c_char_p: "const char*", None: "void"}
+_PRELUDE = """#include <cstddef>
+#include <tuple>
+#include <type_traits>
+#include "%s"
+template <class F> struct sig;
+template <class R, class... A> struct sig<R (*)(A...)> {
+  using ret = R;
+  static constexpr int arity = sizeof...(A);
+  template <int i> using arg = std::tuple_element_t<i, std::tuple<A...>>;
+};
+template <class P> using pointee = std::remove_cv_t<std::remove_pointer_t<P>>;
+#define SAME(...) static_assert(std::is_same<__VA_ARGS__>::value, #__VA_ARGS__)
+#define PTR(...) static_assert(std::is_pointer<__VA_ARGS__>::value, #__VA_ARGS__)
+"""
+
+
+def binding_facts(sigs, structs):
+    """One static_assert per fact of a binding -- sigs {symbol: (restype, [argtypes])}, structs {C name: ctypes class} -- in a C++ unit
+    that includes the header: size of every struct, offset / size / type of every field, arity of every function, every scalar parameter
+    and return type exactly, every pointer parameter a pointer, to the very struct where the binding types it"""
+    from tpgsr_amd import _lib
+    cname = {cls: c for c, cls in list(_lib._CLASSES.items()) + list(structs.items())}
+
+    def typed(expr, t):
+        if t in _CXX:
+            return [f"SAME({expr}, {_CXX[t]});"]
+        if t in cname:                                                             # a nested struct, by value
+            return [f"SAME({expr}, {cname[t]});"]
+        if t is ctypes.c_void_p:
+            return [f"PTR({expr});"]
+        return [f"PTR({expr});", f"SAME(pointee<{expr}>, {cname[t._type_]});"]      # POINTER(struct)
+
+    out = [_PRELUDE % os.path.join(ROOT, "include", "tpgsr_hip.h")]
+    for c, cls in structs.items():
+        out.append(f"static_assert(sizeof({c}) == {ctypes.sizeof(cls)}, \"sizeof {c}\");")
+        for name, t in cls._fields_:
+            f, d = name[:-1] if name.endswith("_") and keyword.iskeyword(name[:-1]) else name, getattr(cls, name)
+            out.append(f"static_assert(offsetof({c}, {f}) == {d.offset} && sizeof({c}::{f}) == {d.size}, \"{c}.{f}\");")
+            out += typed(f"decltype({c}::{f})", t)
+    for name, (res, args) in sigs.items():
+        out.append(f"static_assert(sig<decltype(&{name})>::arity == {len(args)}, \"arity of {name}\");")
+        out += typed(f"sig<decltype(&{name})>::ret", res)
+        for i, t in enumerate(args):
+            out += typed(f"sig<decltype(&{name})>::arg<{i}>", t)
+    return "\n".join(out) + "\n"
+
+
+def compiles(unit, tmp_path):
+    """host-only syntax check by the compiler that builds the library: no device code, no linking, no GPU"""
+    from tpgsr_amd import build
+    src = tmp_path / "abi_facts.cpp"
+    src.write_text(unit)
+    r = subprocess.run([build._hipcc(), "-x", "c++", "-std=c++17", "-fsyntax-only", str(src)], capture_output=True, text=True)
+    return r.returncode == 0, r.stdout + r.stderr
+
+
+def derived_binding():
+    from tpgsr_amd import _lib
+    return dict(_lib._SIGS), dict(_lib._CLASSES)
+
+
+def test_derived_binding_is_what_the_compiler_reads(tmp_path):
+    sigs, structs = derived_binding()
+    assert len(sigs) >= 150 and len(structs) == 13
+    unit = binding_facts(sigs, structs)
+    assert unit.count("static_assert") + unit.count("SAME(") + unit.count("PTR(") > 1400
+    ok, log = compiles(unit, tmp_path)
+    assert ok, log
+
+
+def test_compiler_check_catches_a_wrong_width(tmp_path):
+    """mutant: `long long count` of tpgsr_bn_finalize transcribed as int -- same name, same arity, truncates on the GPU"""
+    sigs, structs = derived_binding()
+    res, args = sigs["tpgsr_bn_finalize"]
+    assert args[3] is ctypes.c_longlong
+    sigs["tpgsr_bn_finalize"] = (res, args[:3] + [ctypes.c_int] + args[4:])
+    ok, log = compiles(binding_facts(sigs, structs), tmp_path)
+    assert not ok and "tpgsr_bn_finalize" in log and "arg<3>" in log, log
+
+
+def test_compiler_check_catches_swapped_fields(tmp_path):
+    """mutant: two adjacent int fields of tpgsr_conv_route_t swapped -- sizeof, all that was compared before, does not change"""
+    sigs, structs = derived_binding()
+    fields = list(structs["tpgsr_conv_route_t"]._fields_)
+    i = [f for f, _ in fields].index("lcap")
+    assert fields[i][1] is fields[i + 1][1] is ctypes.c_int
+    fields[i], fields[i + 1] = fields[i + 1], fields[i]
+    mutant = type("ConvRoute", (ctypes.Structure,), {"_fields_": fields})
+    assert ctypes.sizeof(mutant) == ctypes.sizeof(structs["tpgsr_conv_route_t"])
+    structs["tpgsr_conv_route_t"] = mutant
+    ok, log = compiles(binding_facts(sigs, structs), tmp_path)
+    assert not ok and "tpgsr_conv_route_t.lcap" in log and "tpgsr_conv_route_t.nbw" in log, log
+
+
+SNIPPET = """
+#ifndef X_H
+#define X_H
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define X_ON 1   /* a constant */
+#define X_OFF -2
+enum x_kind { X_A = 0, X_B = 1, X_C };
+typedef struct {
+  const float *in, *in2;     /* pointer attached to the name */
+  float* out;                /* ... and to the type */
+  int N, H,
+      W;
+  unsigned long long seed;
+} x_args;
+typedef struct x_outer { x_args a; double f; const x_args* next; } x_outer;
+typedef union x_val { const void* p; long long i; } x_val;
+int x_run(const x_args* a, const x_outer *o,
+          long long n, unsigned long long seed, void* stream);
+int x_table(const x_args* items_dev, int* const* steps, const unsigned int* mask);
+const char* x_name(void);
+void x_set(int on);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_reader_on_snippets():
+    from tpgsr_amd import _abi
+    h = _abi.parse(SNIPPET)
+    assert h.defines == {"X_ON": 1, "X_OFF": -2}
+    assert h.enums == {"x_kind": [("X_A", 0), ("X_B", 1), ("X_C", 2)]}
+    assert list(h.structs) == ["x_args", "x_outer", "x_val"]                        # declaration order
+    assert h.structs["x_args"] == ("struct", [("in", "const float*"), ("in2", "const float*"), ("out", "float*"), ("N", "int"), ("H", "int"),
+                                              ("W", "int"), ("seed", "unsigned long long")])
+    assert h.structs["x_outer"] == ("struct", [("a", "x_args"), ("f", "double"), ("next", "const x_args*")])     # nested, by name
+    assert h.structs["x_val"] == ("union", [("p", "const void*"), ("i", "long long")])
+    assert h.functions["x_run"] == ("int", [("const x_args*", "a"), ("const x_outer*", "o"), ("long long", "n"),
+                                            ("unsigned long long", "seed"), ("void*", "stream")])                # wrapped over two lines
+    assert h.functions["x_table"] == ("int", [("const x_args*", "items_dev"), ("int* const*", "steps"), ("const unsigned int*", "mask")])
+    assert h.functions["x_name"] == ("const char*", []) and h.functions["x_set"] == ("void", [("int", "on")])
+    assert list(h.functions) == ["x_run", "x_table", "x_name", "x_set"]
+
+
+@pytest.mark.parametrize("bad", ["int x_cb(void (*fn)(int), void* stream);", "int x_arr(const int dims[4]);", "typedef struct { int a : 3; } x_bits;",
+                                 "typedef struct { int v[4]; } x_vec;", "size_t x_bytes(void);", "int x_old();", "int x_unnamed(int, float);",
+                                 "typedef int x_int;", "static const int x_k = 3;", "#define X_F 1.5f", "#include <stddef.h>",
+                                 "typedef struct { struct x_in { int a; } in; } x_nest;", "int x_run(const x_other* a);",
+                                 "enum x_e { X_Q = 1 << 2 };", "int x_dup(int a); int x_dup(int a);"])
+def test_header_reader_raises_on_what_it_cannot_read(bad):
+    """a declaration outside the subset fails loudly and is named: it must never drop out of the binding silently"""
+    from tpgsr_amd import _abi
+    good = "int x_before(int a);\n%s\nint x_after(int b);\n"
+    assert list(_abi.parse(good % "").functions) == ["x_before", "x_after"]
+    with pytest.raises(_abi.HeaderError) as e:
+        _abi.parse(good % bad)
+    named = re.findall(r"x_\w+|X_\w+|stddef", bad)[0]
+    assert named in str(e.value), str(e.value)
+
+
+def test_type_mapping_of_the_binding():
+    """the header's conventions as ctypes: struct pointers typed, device-resident tables (`*_dev`) and every other pointer an address"""
+    from tpgsr_amd import _lib
+    P, vp, ci, ll = ctypes.POINTER, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    S = _lib._SIGS
+    assert S["tpgsr_conv_fwd"] == (ci, [P(_lib.ConvArgs), vp])
+    assert S["tpgsr_conv_wgrad_batch"] == (ci, [vp, ci, ci, ci, ci, vp])                       # items_dev
+    assert S["tpgsr_conv_wgrad_batch_prepare"] == (ci, [P(_lib.WgradArgs), P(_lib.WgradBatchItem)])
+    assert S["tpgsr_resize_normalize"][1][:3] == [vp, vp, vp]                                  # pixels, descs_dev, tables_dev
+    assert S["tpgsr_wgrad_halo_plan"] == (ci, [P(_lib.ConvArgs), vp, vp])
+    assert S["tpgsr_plan_set_mode"] == (None, [ci, ci, ctypes.c_ulonglong, ci])
+    assert S["tpgsr_lstm_seq_hx_bytes"] == (ll, []) and S["tpgsr_last_error"] == (ctypes.c_char_p, [])
+    assert S["tpgsr_plan_create"] == (vp, []) and S["tpgsr_plan_add_launch"][1] == [vp, ctypes.c_char_p, P(_lib.PlanArg), ci, ci]
+    assert S["tpgsr_bn_finalize"][1][3] is ll and S["tpgsr_add"][1][2] is ll
+    assert _lib.ConvArgs._fields_[0] == ("in_", vp) and _lib.WgradArgs._fields_[0] == ("c", _lib.ConvArgs)
+    assert issubclass(_lib.PlanArg, ctypes.Union) and _lib.PlanArg._fields_ == [("p", vp), ("i", ll), ("f", ctypes.c_double)]
+    assert _lib.CONV_KERNELS[5] == "xbf_halo3" and _lib.WGRAD_KERNELS[4] == "xbf_3k" and len(_lib.CONV_KERNELS) == 9
+    assert (_lib.ACT_NONE, _lib.ACT_RELU, _lib.ACT_MISH, _lib.ACT_TANH, _lib.ACT_PRELU) == (0, 1, 2, 3, 4)
+    for arg in (ctypes.byref(ll()), (ctypes.c_float * 2)(), ctypes.pointer(ci()), 0x1000, None):  # what callers hand to an address parameter
+        vp.from_param(arg)
 
 
 def test_error_reporting_without_gpu(lib):

@@ -28,6 +28,9 @@ extern "C" int tpgsr_sizeof(int which) {
     case 7: return (int)sizeof(tpgsr_gru_wgrad_args);
     case 8: return (int)sizeof(tpgsr_wgrad_batch_item);
     case 9: return (int)sizeof(tpgsr_bigru_proj_args);
+    case 10: return (int)sizeof(tpgsr_conv_route_t);
+    case 11: return (int)sizeof(tpgsr_wgrad_route_t);
+    case 12: return (int)sizeof(tpgsr_plan_arg);
     default: return -1;
   }
 }
