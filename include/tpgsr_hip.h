@@ -676,6 +676,15 @@ int tpgsr_resample_ksize(int in_size, int out_size);
 int tpgsr_resample_coeffs(int in_size, int out_size, int* bounds, int* kk);
 int tpgsr_resize_normalize(const unsigned char* pixels, const tpgsr_image_desc* descs_dev, const int* tables_dev, int N, int OH, int OW,
                            int maxH, int mask, unsigned char* tmp, unsigned char* res8, float* out, void* stream);
+/* The `--syn` collate's first step (dataset/dataset.py:984-986 `image.resize((w // s, h // s), Image.BICUBIC)`): the same two-pass
+ * 8-bit resize, every image to its OWN size, uint8 HWC in and out.  src_descs[n] is what tpgsr_resize_normalize takes (offset, H, W
+ * of the source in `pixels`, tables W -> w1 and H -> h1); dst_descs[n] holds offset = byte offset of image n's [h1][w1][3] result in
+ * out8, H = h1, W = w1.  The table fields of dst_descs are NOT read here: the caller fills them with the next stage's tables
+ * (w1 -> OW, h1 -> OH), and the same device array is then the descriptor input of tpgsr_resize_normalize(out8, dst_descs_dev, ...).
+ * maxH = max H, maxOH = max h1, maxOW = max w1 over the batch; tmp: horizontal-pass scratch, padded [N][maxH][maxOW][3] (image n
+ * uses rows < H_n, columns < w1_n; the rest is neither written nor read).  A pass whose sizes are equal is an identity by its table. */
+int tpgsr_resize_ragged(const unsigned char* pixels, const tpgsr_image_desc* src_descs_dev, const tpgsr_image_desc* dst_descs_dev,
+                        const int* tables_dev, int N, int maxH, int maxOH, int maxOW, unsigned char* tmp, unsigned char* out8, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Evaluation path (interfaces/super_resolution.py:540-900): CTC greedy decoding of the recogniser's logits

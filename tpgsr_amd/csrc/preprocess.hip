@@ -4,6 +4,7 @@
 // (two separable passes in 22-bit fixed point with a clamp after each, src/libImaging/Resample.c: restated in
 // oracle/input_pipeline.py and pinned against the installed Pillow).  The reference runs this per image with PIL on ONE
 // DataLoader worker (`workers: 1`); here the host only concatenates the encoded-size uint8 pixels and the coefficient tables.
+// tpgsr_resize_ragged is the same resize to a PER-IMAGE size, uint8 out: the first step of the `--syn` collate (dataset/dataset.py:952-992).
 #include "common.h"
 #include <math.h>
 
@@ -72,6 +73,36 @@ __device__ __forceinline__ unsigned char rs_clip8(int acc) {
   return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
+// one output pixel of a pass: `taps` input pixels (3 bytes each, `stride` bytes apart) weighted by k[], accumulated from 2^21, clamped
+__device__ __forceinline__ void rs_taps3(const unsigned char* __restrict__ p, size_t stride, const int* __restrict__ k, int taps,
+                                         unsigned char& v0, unsigned char& v1, unsigned char& v2) {
+  int a0 = 1 << (RS_PRECISION_BITS - 1), a1 = a0, a2 = a0;
+  for (int x = 0; x < taps; ++x) {
+    const int kv = k[x];
+    const unsigned char* q = p + x * stride;
+    a0 += q[0] * kv;
+    a1 += q[1] * kv;
+    a2 += q[2] * kv;
+  }
+  v0 = rs_clip8(a0);
+  v1 = rs_clip8(a1);
+  v2 = rs_clip8(a2);
+}
+
+// horizontal pass of image d, row y, output column xx (row stride of the source: d.W pixels)
+__device__ __forceinline__ void rs_row3(const unsigned char* __restrict__ pix, const tpgsr_image_desc& d, const int* __restrict__ tab, int y,
+                                        int xx, unsigned char* __restrict__ o) {
+  const int* b = tab + d.xb_off + 2 * xx;
+  rs_taps3(pix + d.offset + ((size_t)y * d.W + b[0]) * 3, 3, tab + d.xk_off + xx * d.kx, b[1], o[0], o[1], o[2]);
+}
+
+// vertical pass of image d, output row yy: `img` is the image's horizontal-pass result, rows `rowpix` pixels apart, at column xx
+__device__ __forceinline__ void rs_col3(const unsigned char* __restrict__ img, size_t rowpix, const tpgsr_image_desc& d,
+                                        const int* __restrict__ tab, int yy, unsigned char& v0, unsigned char& v1, unsigned char& v2) {
+  const int* b = tab + d.yb_off + 2 * yy;
+  rs_taps3(img + (size_t)b[0] * rowpix * 3, rowpix * 3, tab + d.yk_off + yy * d.ky, b[1], v0, v1, v2);
+}
+
 // horizontal pass: tmp[n][y][xx][c], y < H_n
 __global__ __launch_bounds__(256) void resize_h_kernel(const unsigned char* __restrict__ pix, const tpgsr_image_desc* __restrict__ descs,
                                                        const int* __restrict__ tab, int N, int OW, int maxH, unsigned char* __restrict__ tmp) {
@@ -83,20 +114,7 @@ __global__ __launch_bounds__(256) void resize_h_kernel(const unsigned char* __re
     const int n = (int)(r / maxH);
     const tpgsr_image_desc d = descs[n];
     if (y >= d.H) continue;
-    const int* b = tab + d.xb_off + 2 * xx;
-    const int* k = tab + d.xk_off + xx * d.kx;
-    const unsigned char* row = pix + d.offset + ((size_t)y * d.W + b[0]) * 3;
-    int a0 = 1 << (RS_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-    for (int x = 0; x < b[1]; ++x) {
-      const int kv = k[x];
-      a0 += row[3 * x] * kv;
-      a1 += row[3 * x + 1] * kv;
-      a2 += row[3 * x + 2] * kv;
-    }
-    unsigned char* o = tmp + (((size_t)n * maxH + y) * OW + xx) * 3;
-    o[0] = rs_clip8(a0);
-    o[1] = rs_clip8(a1);
-    o[2] = rs_clip8(a2);
+    rs_row3(pix, d, tab, y, xx, tmp + (((size_t)n * maxH + y) * OW + xx) * 3);
   }
 }
 
@@ -111,18 +129,8 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const unsigned char* __re
     const int yy = (int)(r % OH);
     const int n = (int)(r / OH);
     const tpgsr_image_desc d = descs[n];
-    const int* b = tab + d.yb_off + 2 * yy;
-    const int* k = tab + d.yk_off + yy * d.ky;
-    const unsigned char* col = tmp + (((size_t)n * maxH + b[0]) * OW + xx) * 3;
-    int a0 = 1 << (RS_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-    for (int y = 0; y < b[1]; ++y) {
-      const int kv = k[y];
-      const unsigned char* p = col + (size_t)y * OW * 3;
-      a0 += p[0] * kv;
-      a1 += p[1] * kv;
-      a2 += p[2] * kv;
-    }
-    const unsigned char v0 = rs_clip8(a0), v1 = rs_clip8(a1), v2 = rs_clip8(a2);
+    unsigned char v0, v1, v2;
+    rs_col3(tmp + ((size_t)n * maxH * OW + xx) * 3, OW, d, tab, yy, v0, v1, v2);
     unsigned char* o8 = res8 + i * 3;
     o8[0] = v0; o8[1] = v1; o8[2] = v2;
     const size_t plane = (size_t)OH * OW;
@@ -130,6 +138,42 @@ __global__ __launch_bounds__(256) void resize_v_kernel(const unsigned char* __re
     o[0] = (float)v0 / 255.f;
     o[plane] = (float)v1 / 255.f;
     o[2 * plane] = (float)v2 / 255.f;
+  }
+}
+
+// ---- ragged resize: every image to its OWN size (the `--syn` collate's `image.resize((w // s, h // s))`, dataset/dataset.py:984-986) ----
+// horizontal pass: tmp [N][maxH][maxOW][3], image n fills rows y < H_n, columns xx < dst[n].W; the padding is neither read nor written
+__global__ __launch_bounds__(256) void resize_ragged_h_kernel(const unsigned char* __restrict__ pix, const tpgsr_image_desc* __restrict__ src,
+                                                              const tpgsr_image_desc* __restrict__ dst, const int* __restrict__ tab, int N,
+                                                              int maxH, int maxOW, unsigned char* __restrict__ tmp) {
+  const long long total = (long long)N * maxH * maxOW;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % maxOW);
+    const long long r = i / maxOW;
+    const int y = (int)(r % maxH);
+    const int n = (int)(r / maxH);
+    const tpgsr_image_desc d = src[n];
+    if (y >= d.H || xx >= dst[n].W) continue;
+    rs_row3(pix, d, tab, y, xx, tmp + i * 3);
+  }
+}
+
+// vertical pass: out8 + dst[n].offset is image n's [h1][w1][3]
+__global__ __launch_bounds__(256) void resize_ragged_v_kernel(const unsigned char* __restrict__ tmp, const tpgsr_image_desc* __restrict__ src,
+                                                              const tpgsr_image_desc* __restrict__ dst, const int* __restrict__ tab, int N,
+                                                              int maxH, int maxOH, int maxOW, unsigned char* __restrict__ out8) {
+  const long long total = (long long)N * maxOH * maxOW;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % maxOW);
+    const long long r = i / maxOW;
+    const int yy = (int)(r % maxOH);
+    const int n = (int)(r / maxOH);
+    const long long ooff = dst[n].offset;
+    const int h1 = dst[n].H, w1 = dst[n].W;
+    if (yy >= h1 || xx >= w1) continue;
+    const tpgsr_image_desc d = src[n];
+    unsigned char* o = out8 + ooff + ((size_t)yy * w1 + xx) * 3;
+    rs_col3(tmp + ((size_t)n * maxH * maxOW + xx) * 3, maxOW, d, tab, yy, o[0], o[1], o[2]);
   }
 }
 
@@ -165,4 +209,18 @@ extern "C" int tpgsr_resize_normalize(const unsigned char* pixels, const tpgsr_i
                      maxH, C, res8, out);
   if (mask) hipLaunchKernelGGL(luma_mask_kernel, dim3(N), dim3(256), 0, st, res8, OH, OW, C, out);
   TPGSR_LAUNCH_CHECK("tpgsr_resize_normalize");
+}
+
+extern "C" int tpgsr_resize_ragged(const unsigned char* pixels, const tpgsr_image_desc* src_descs_dev, const tpgsr_image_desc* dst_descs_dev,
+                                   const int* tables_dev, int N, int maxH, int maxOH, int maxOW, unsigned char* tmp, unsigned char* out8,
+                                   void* stream) {
+  TPGSR_CHECK_ARG(pixels && src_descs_dev && dst_descs_dev && tables_dev && tmp && out8 && N > 0 && maxH > 0 && maxOH > 0 && maxOW > 0,
+                  "tpgsr_resize_ragged: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  long long t1 = (long long)N * maxH * maxOW, t2 = (long long)N * maxOH * maxOW;
+  hipLaunchKernelGGL(resize_ragged_h_kernel, dim3((int)min((long long)4096, (t1 + 255) / 256)), dim3(256), 0, st, pixels, src_descs_dev,
+                     dst_descs_dev, tables_dev, N, maxH, maxOW, tmp);
+  hipLaunchKernelGGL(resize_ragged_v_kernel, dim3((int)min((long long)4096, (t2 + 255) / 256)), dim3(256), 0, st, tmp, src_descs_dev,
+                     dst_descs_dev, tables_dev, N, maxH, maxOH, maxOW, out8);
+  TPGSR_LAUNCH_CHECK("tpgsr_resize_ragged");
 }

@@ -1081,6 +1081,12 @@ def strip_resample_fwd(inp, scale, shift, act, N, Win, Wout, C_, out):
     _launch("tpgsr_strip_resample_fwd", _p(inp), _p(scale), _p(shift), act_code(act), N, Win, Wout, C_, _p(out))
 
 
+def resize_ragged(pix, src_descs, dst_descs, tables, N, maxH, maxOH, maxOW, tmp, out8):
+    """Pillow's 8-bit bicubic resize of N uint8 HWC images, each to the size its dst descriptor names (tpgsr_amd/data.py builds both arrays)"""
+    assert tmp.numel() >= N * maxH * maxOW * 3, "tmp is the padded [N][maxH][maxOW][3] scratch of the horizontal pass"
+    _launch("tpgsr_resize_ragged", _p(pix), _p(src_descs), _p(dst_descs), _p(tables), N, maxH, maxOH, maxOW, _p(tmp), _p(out8))
+
+
 def strip_resample_bwd(inp, scale, shift, act, dout, N, Win, Wout, C_, dz):
     _launch("tpgsr_strip_resample_bwd", _p(inp), _p(scale), _p(shift), act_code(act), _p(dout), N, Win, Wout, C_, _p(dz))
 
