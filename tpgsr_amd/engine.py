@@ -793,6 +793,9 @@ class TSRNEngine(_EngineBase):
     def __init__(self, module: torch.nn.Module, grid_align_corners: bool = False):
         super().__init__(module)
         self.grid_align_corners = grid_align_corners
+        # SR grid / LR grid = 2 ** (number of UpsampleBLocks in front of the tail convolution); the train steps and the evaluator size
+        # their buffers with it before the first bind
+        self.scale = 2 ** (len(getattr(module, f"block{module.srb_nums + 3}")) - 1)
         # weight-gradient launches on a second stream (Plan.side).  Needs every buffer a wgrad reads to be written once
         # per backward pass: _record_bwd gives each layer its own dy / du / dgi / dgh instead of recycling one set.
         self.overlap_wgrad = os.environ.get("TPGSR_OVERLAP_WGRAD", "1") != "0"
@@ -843,10 +846,12 @@ class TSRNEngine(_EngineBase):
         self.conv7 = ConvLayer(self, k7 + ".0.weight", k7 + ".0.bias", 3, 3, 1, 1)
         self.bn7 = BNLayer(self, k7 + ".1")
         k8 = f"block{self.srb + 3}"
+        # one UpsampleBLock (conv3x3 C -> 4C, PixelShuffle(2), mish) per factor of two: scale_factor = 2 ** n_up (model/tsrn.py:25, :42, :158)
         self.n_up = len([k for k in self.P if k.startswith(k8 + ".") and k.endswith(".conv.weight")])
-        if self.n_up != 1:
-            raise NotImplementedError("scale_factor != 2 is not on the TPGSR hot path (reference configs use 2)")
-        self.up = ConvLayer(self, k8 + ".0.conv.weight", k8 + ".0.conv.bias", 3, 3, 1, 1)
+        if self.n_up < 1:
+            raise NotImplementedError("TSRN without an up-sampling block (scale_factor = 1) is not on the TPGSR hot path")
+        assert self.scale == 2 ** self.n_up
+        self.ups = [ConvLayer(self, f"{k8}.{k}.conv.weight", f"{k8}.{k}.conv.bias", 3, 3, 1, 1) for k in range(self.n_up)]
         self.tail = ConvLayer(self, f"{k8}.{self.n_up}.weight", None, tail=True)
         self.tail_bias = self.P[f"{k8}.{self.n_up}.bias"]
         if self.stn:
@@ -957,13 +962,25 @@ class TSRNEngine(_EngineBase):
         part, _ = self.bn7.partial(P1)
         g7 = self.conv7.fwd(N, H, W, cur, y7, bn_partial=part if training else None, bn_coarse=training)
         self.bn7.finalize(P1, self.conv7.b, training, g7.bn_row_tiles)
-        ups = ws("ups", 4 * P1, Cc)                      # pre-mish, pixel-shuffled [N][2H][2W][C]
-        self.up.fwd(N, H, W, y7, ups, in2=b1, out_ps=True, **self.bn7.loader)
-        mu = ws("mups", 4 * P1, Cc)                      # mish(ups) once (the 9-tap tail conv and its wgrad both read it)
-        K.affine_act(ups, 4 * P1, Cc, None, None, "mish", mu)
-        Pt = ws("Pt", 4 * P1, self.tail.Cout)
-        self.tail.fwd(N, 2 * H, 2 * W, mu, Pt)
-        K.tail_shiftsum_tanh(Pt, self.tail_bias, N, 2 * H, 2 * W, self.tail.Co, self.tail.KS, K.DynPtr("sr"))
+        # the up-sampling stages: stage 0 reads bn7(y7) + b1 through its loader, stage k > 0 reads mish(ups_{k-1}) at 2^k H x 2^k W
+        mu, h, w = None, H, W
+        for k, up in enumerate(self.ups):
+            ups = ws(self._up_name("ups", k), 4 * N * h * w, Cc)      # pre-mish, pixel-shuffled [N][2h][2w][C]
+            if k == 0:
+                up.fwd(N, h, w, y7, ups, in2=b1, out_ps=True, **self.bn7.loader)
+            else:
+                up.fwd(N, h, w, mu, ups, out_ps=True)
+            mu = ws(self._up_name("mups", k), 4 * N * h * w, Cc)      # mish(ups) once (the next 9-tap conv and its wgrad both read it)
+            K.affine_act(ups, 4 * N * h * w, Cc, None, None, "mish", mu)
+            h, w = 2 * h, 2 * w
+        Pt = ws("Pt", N * h * w, self.tail.Cout)
+        self.tail.fwd(N, h, w, mu, Pt)
+        K.tail_shiftsum_tanh(Pt, self.tail_bias, N, h, w, self.tail.Co, self.tail.KS, K.DynPtr("sr"))
+
+    @staticmethod
+    def _up_name(name, k):
+        """workspace of up-sampling stage k (stage 0 keeps the names of the one-stage network)"""
+        return name if k == 0 else f"{name}{k}"
 
     def _ig_widths(self, Wp):
         ws_ = [Wp]
@@ -1052,8 +1069,10 @@ class TSRNEngine(_EngineBase):
     # ---- backward ------------------------------------------------------------------------------------------------
     def _record_bwd(self, N, H, W, ws):
         Cc, Ci = self.C, self.in_planes
-        P1, P4 = N * H * W, 4 * N * H * W
-        H2, W2 = 2 * H, 2 * W
+        P1 = N * H * W
+        H2, W2 = self.scale * H, self.scale * W         # the SR grid
+        P4 = N * H2 * W2
+        last = self.n_up - 1
         t = ws.t
         tl = self.tail
         # tail: dP, bias grad, weight grad, d mish(ups)
@@ -1064,18 +1083,33 @@ class TSRNEngine(_EngineBase):
         K.tail_bwd(K.DynPtr("sr"), K.DynPtr("dsr"), N, H2, W2, tl.Co, tl.KS, dPt, dbp, nblk)
         with K.side():   # bias gradient: a leaf, off the critical path
             K.reduce_partials(dbp, nblk, tl.Co, self.G[tl.wname.replace(".weight", ".bias")], accumulate=True)
-        tl.wgrad(N, H2, W2, t["mups"], dPt)
-        dm = ws("d_ups", P4, Cc)
+        tl.wgrad(N, H2, W2, t[self._up_name("mups", last)], dPt)
+        dm = ws(self._up_name("d_ups", last), P4, Cc)
+        y_up = t[self._up_name("ups", last)]
         if K.bnb_fusable(tl.Cout):     # d(ups) = mish'(ups) * (data gradient), the factor applied in the convolution's epilogue
-            tl.dgrad(N, H2, W2, dPt, dm, bnb=dict(y=t["ups"], act="mish", store_dz=True))
+            tl.dgrad(N, H2, W2, dPt, dm, bnb=dict(y=y_up, act="mish", store_dz=True))
         else:
             tl.dgrad(N, H2, W2, dPt, dm)
-            K.act_bwd(t["ups"], dm, P4 * Cc, "mish", dm)                  # in place: d(ups), pixel-shuffled layout
-        # upsample conv: input was bn7(y7) + b1
-        self.up.wgrad(N, H, W, t["y7"], dm, loader=dict(in2=t["b1"], **self.bn7.loader), dy_kw=dict(dy_ps=True))
+            K.act_bwd(y_up, dm, P4 * Cc, "mish", dm)                      # in place: d(ups), pixel-shuffled layout
+        # up-sampling stages k > 0, last first: input was mish(ups_{k-1}) on the 2^k H x 2^k W grid
+        for k in range(last, 0, -1):
+            up, h, w = self.ups[k], H << k, W << k
+            Pk = N * h * w
+            up.wgrad(N, h, w, t[self._up_name("mups", k - 1)], dm, dy_kw=dict(dy_ps=True))
+            dprev = ws(self._up_name("d_ups", k - 1), Pk, Cc)
+            y_up = t[self._up_name("ups", k - 1)]
+            if K.bnb_fusable(up.Cout):
+                up.dgrad(N, h, w, dm, dprev, in_ps=True, bnb=dict(y=y_up, act="mish", store_dz=True))
+            else:
+                up.dgrad(N, h, w, dm, dprev, in_ps=True)
+                K.act_bwd(y_up, dprev, Pk * Cc, "mish", dprev)
+            dm = dprev
+        # first upsample conv: input was bn7(y7) + b1
+        up0 = self.ups[0]
+        up0.wgrad(N, H, W, t["y7"], dm, loader=dict(in2=t["b1"], **self.bn7.loader), dy_kw=dict(dy_ps=True))
         d_s = ws("d_s", P1, Cc)                                           # = d(bn7 out) = one of b1's gradients
-        fz7 = self.bn7.fuse_stats(t["y7"], P1, "none", self.up.Cout)
-        self.up.dgrad(N, H, W, dm, d_s, in_ps=True, bnb=fz7)
+        fz7 = self.bn7.fuse_stats(t["y7"], P1, "none", up0.Cout)
+        up0.dgrad(N, H, W, dm, d_s, in_ps=True, bnb=fz7)
         uniq = self.overlap_wgrad
 
         def buf(name, tag, C_):    # one buffer per use when a side-stream wgrad reads it, else one recycled buffer
@@ -1243,7 +1277,7 @@ class TSRNEngine(_EngineBase):
         N, _, H, W = x.shape
         pl = self.plans(N, H, W, training, slot, defer_join and training)
         x = x.contiguous().float()
-        sr = torch.empty(N, self.in_planes, 2 * H, 2 * W, dtype=F32, device=x.device)
+        sr = torch.empty(N, self.in_planes, self.scale * H, self.scale * W, dtype=F32, device=x.device)
         if not pre_done:
             pl["pre"].set_ptr("x", x.data_ptr())
             if not training:

@@ -184,6 +184,7 @@ class FunctionalSREngine(FunctionalEngine):
     Otherwise operator by operator through autograd: the reference implementation of the recorded mode."""
     FUSED = False
     role = "sr"
+    scale = 2            # SR grid / LR grid: the operator-level backbones are built for the reference's x2 only (DESIGN section 7)
 
     def __init__(self, module: torch.nn.Module):
         super().__init__(module)

@@ -68,6 +68,21 @@ def _image_crit_grad(image_crit, sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, 
         K.image_loss_bwd(sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, dsr)
 
 
+def _sr_scale(who, modules) -> int:
+    """SR grid / LR grid of a step's SR network(s) (`scale` of their engines: 2 ** up-sampling stages for TSRN / TSRN_TL, 2 for the
+    operator-level backbones); every stage of a cascade compares with the same HR batch, so they must agree"""
+    scales = sorted({int(m._engine().scale) for m in modules})
+    if len(scales) != 1:
+        raise ValueError(f"{who}: the SR networks of one cascade disagree on scale_factor ({scales})")
+    return scales[0]
+
+
+def _check_hr(who, hr, N, C, H, W, s):
+    if tuple(hr.shape) != (N, C, s * H, s * W):
+        raise ValueError(f"{who}: hr is {tuple(hr.shape)}, expected (N, C, {s}H, {s}W) = {(N, C, s * H, s * W)} for the "
+                         f"{(N, C, H, W)} low-resolution batch of a x{s} network")
+
+
 def _refuse_exchange_with_functional_engine(who, modules, advice):
     from ..engine_functional import FunctionalSREngine
     for m in modules:
@@ -117,12 +132,13 @@ class TSRNTrainStep:
             if self.channels is not None and self.channels > C:
                 raise ValueError(f"TSRNTrainStep: channels={self.channels} of a batch with {C} planes")
             Cs = C if self.channels is None else self.channels
-            self._static = dict(dev=dev, shape=tuple(lr_img.shape),
+            s = _sr_scale("TSRNTrainStep", [self.model])
+            self._static = dict(dev=dev, shape=tuple(lr_img.shape), scale=s,
                                 part=torch.empty(_NBLK_IMG, 2, device=dev), loss=torch.zeros((), device=dev),
-                                dloss=torch.full((1,), 100.0, device=dev), dsr=torch.empty(N, Cs, 2 * H, 2 * W, device=dev),
+                                dloss=torch.full((1,), 100.0, device=dev), dsr=torch.empty(N, Cs, s * H, s * W, device=dev),
                                 inv_world=torch.full((1,), 1.0 / self.world, device=dev))
             if Cs != C:      # the channel prefixes the network and the criterion see
-                self._static.update(lr_c=torch.empty(N, Cs, H, W, device=dev), hr_c=torch.empty(N, Cs, 2 * H, 2 * W, device=dev))
+                self._static.update(lr_c=torch.empty(N, Cs, H, W, device=dev), hr_c=torch.empty(N, Cs, s * H, s * W, device=dev))
         return self._static
 
     @staticmethod
@@ -138,16 +154,16 @@ class TSRNTrainStep:
         eng = model._engine()
         st = self._buffers(lr_img)
         N, C, H, W = lr_img.shape
+        s = st["scale"]
+        _check_hr("TSRNTrainStep", hr_img, N, C, H, W, s)
         self.opt.zero_grad()
         hr = hr_img.contiguous()
         if "lr_c" in st:
-            if tuple(hr.shape) != (N, C, 2 * H, 2 * W):
-                raise ValueError(f"TSRNTrainStep: hr is {tuple(hr.shape)}, expected {(N, C, 2 * H, 2 * W)}")
             self._prefix(lr_img.contiguous(), st["lr_c"])
             self._prefix(hr, st["hr_c"])
             lr_img, hr, C = st["lr_c"], st["hr_c"], st["lr_c"].shape[1]
         sr = eng.forward(lr_img, True)
-        H2, W2 = 2 * H, 2 * W
+        H2, W2 = s * H, s * W
         # the loss VALUE is for the caller's log (the gradient below does not read it): its pass over sr / hr and the single-wave finalize run
         # on the auxiliary stream next to the backward pass, not in front of it
         main, aux = K.current_stream(), K.aux_stream(lr_img.device)
@@ -334,7 +350,8 @@ class TPGSRTrainStep:
         if self._static is None or self._static["key"] != (dev, tuple(lr_img.shape)):
             _, C, H, W = lr_img.shape
             S = self.stu_iter
-            st = dict(key=(dev, tuple(lr_img.shape)), q=torch.empty(N, 26, 37, device=dev),
+            s = _sr_scale("TPGSRTrainStep", self.sr)
+            st = dict(key=(dev, tuple(lr_img.shape)), scale=s, q=torch.empty(N, 26, 37, device=dev),
                       gray_hr=torch.empty(N, 1, 32, 100, device=dev), loss=torch.zeros((), device=dev),
                       dloss=torch.full((1,), 100.0, device=dev), inv_world=torch.full((1,), 1.0 / self.world, device=dev),
                       part_img=[torch.empty(_NBLK_IMG, 2, device=dev) for _ in range(S)],
@@ -343,15 +360,15 @@ class TPGSRTrainStep:
                       gray=[torch.empty(N, 1, 32, 100, device=dev) for _ in range(S)],
                       p=[torch.empty(N, 26, 37, device=dev) for _ in range(S)],
                       prior=[torch.empty(N, 37, 1, 26, device=dev) for _ in range(S)],
-                      dsr=[torch.empty(N, C, 2 * H, 2 * W, device=dev) for _ in range(S)],
-                      dcas=torch.empty(N, C, 2 * H, 2 * W, device=dev), dlogits=torch.empty(N, 26, 37, device=dev))
+                      dsr=[torch.empty(N, C, s * H, s * W, device=dev) for _ in range(S)],
+                      dcas=torch.empty(N, C, s * H, s * W, device=dev), dlogits=torch.empty(N, 26, 37, device=dev))
             if self.use_label:
                 st.update(ctc_nll=[torch.empty(N, device=dev) for _ in range(S)])
             if self.ssim_loss:
                 from ..utils.ssim_psnr import create_window
                 cc = min(C, 3)
                 st.update(ssim_win=create_window(11, 1)[0, 0].contiguous().to(dev), ssim_part=torch.empty(256, dtype=torch.float64, device=dev),
-                          ssim_out=torch.empty(1, device=dev), ssim_gm=torch.empty(3 * N * cc * 4 * H * W, device=dev))
+                          ssim_out=torch.empty(1, device=dev), ssim_gm=torch.empty(3 * N * cc * s * s * H * W, device=dev))
             self._static = st
         return self._static
 
@@ -376,7 +393,8 @@ class TPGSRTrainStep:
         N, C, H, W = lr_img.shape
         ctc = self._labels(labels, N, lr_img.device) if self.use_label else None
         wsem = 100.0 if self.use_distill else 0.0
-        H2, W2 = 2 * H, 2 * W
+        H2, W2 = st["scale"] * H, st["scale"] * W
+        _check_hr("TPGSRTrainStep", hr_img, N, C, H, W, st["scale"])
         hr = hr_img.contiguous()
         lr_img = lr_img.contiguous().float()
         if self.collective:
@@ -719,6 +737,7 @@ class TextSREvaluator:
                 lr = lr_c
             return [srm._engine().forward(lr, False)], []
         cascade, ch, cw = lr, H, W
+        s = _sr_scale("TextSREvaluator", self.sr[:1] if self.sr_share else self.sr[:self.stu_iter])      # (the networks the stages run)
         srs, priors = [], []
         for i in range(self.stu_iter):
             tpg = self.tpg[0 if self.tpg_share else i]
@@ -732,7 +751,7 @@ class TextSREvaluator:
             sr = srm._engine().forward(lr, False, prior)
             srs.append(sr)
             priors.append(p)
-            cascade, ch, cw = sr, 2 * H, 2 * W
+            cascade, ch, cw = sr, s * H, s * W
         return srs, priors
 
     @torch.no_grad()
