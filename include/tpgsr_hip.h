@@ -337,6 +337,23 @@ int tpgsr_embed_concat(const int* ids, const float* emb, int V, int E, const flo
 int tpgsr_gru_cell(const float* gi, const float* gh, const float* h, int N, int Hd, float* hnew, void* stream);
 /* greedy decision (:60-61): ids[n*ld+col] = first arg-max of logits[n], score[n*ld+col] = its softmax probability; ids_next (optional) [N] */
 int tpgsr_softmax_max(const float* logits, int N, int C, int* ids, float* score, int ld, int col, int* ids_next, void* stream);
+/* Beam-search decode (AttentionRecognitionHead.beam_search, attention_recognition_head.py:68-184): N images, B beams, C classes,
+ * L steps, row r = n * B + b, R = N * B.  1 <= B <= 8, C >= 1, B * C <= 512, L >= 1.  Every selection orders by higher value, then
+ * LOWER index; a NaN counts as -inf; -inf candidates are taken in index order once the finite ones run out. */
+/* tpgsr_aster_attention for R decoder rows of which row r reads xproj / x of sequence r / rows_per_seq (xproj [R / rows_per_seq][T][A],
+ * x [R / rows_per_seq][T][D], sproj [R][A] -> alpha [R][T], context [R][D]); rows_per_seq = 1 is tpgsr_aster_attention bit for bit */
+int tpgsr_aster_attention_rows(const float* xproj, const float* sproj, const float* wv, const float* bv, const float* x, int R,
+                               int rows_per_seq, int T, int A, int D, float* alpha, float* context, void* stream);
+/* one time step: candidates seq[r] + log_softmax(logits[r]) [R][C]; per image the B best of its B * C; the j-th best with flat index f
+ * gives row n * B + j its score_t, sym_t = f % C, pred_t = n * B + f / C, and seq = the score, or -inf where the symbol is eos.
+ * For every input sym_t lies in [0, C) and pred_t in [n * B, n * B + B).  score_t / sym_t / pred_t: [R], one step of an [L][R] history */
+int tpgsr_beam_step(const float* logits, float* seq, int N, int B, int C, int eos, float* score_t, int* sym_t, int* pred_t, void* stream);
+/* dst[r] = src[idx[r]] for R rows of W floats (src != dst; an index outside [0, R) is clamped) */
+int tpgsr_gather_rows(const float* src, const int* idx, int R, int W, float* dst, void* stream);
+/* the backtrack over the [L][R] histories (:124-184): ids_out [N][L] = the best finished or surviving sequence of every image,
+ * best_score [N] its score, best_len [N] its length (t + 1 of its eos, or L) */
+int tpgsr_beam_backtrack(const float* score_hist, const int* sym_hist, const int* pred_hist, int N, int B, int L, int eos, int* ids_out,
+                         float* best_score, int* best_len, void* stream);
 
 /* the whole-CU halo kernel (csrc/conv_halo3.hip: one workgroup per CU on three 64-pixel tiles at once, T <= 2) takes the KH x KW > 1 x 1
  * convolutions whose 192-pixel halo fits LDS and that fill the chip; 0 sends them back to the two-workgroup halo kernel (tests, A/B) */

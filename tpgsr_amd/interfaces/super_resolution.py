@@ -757,7 +757,7 @@ class TextSREvaluator:
     @torch.no_grad()
     def recognize(self, images):
         """evaluation recogniser -> list of strings.  CRNN (`--test_model CRNN`): CTC greedy decoding; an ASTER `RecognizerBuilder`
-        (`--test_model ASTER`, interfaces/super_resolution.py:107-135): parse_aster_data + its greedy attention decode; a `MORAN`
+        (`--test_model ASTER`, interfaces/super_resolution.py:107-135): parse_aster_data + its attention decode (greedy, or the reference's beam search when built with beam_width >= 1); a `MORAN`
         (`--test_model MORAN`): parse_moran_data + rectifier + its left-to-right attention decoder"""
         from ..utils.metrics import get_string_crnn
         from ..model.recognizer import RecognizerBuilder

@@ -1424,3 +1424,22 @@ def gru_cell(gi, gh, h, N, Hd, hnew):
 
 def softmax_max(logits, N, C_, ids, score, ld, col, ids_next=None):
     _launch("tpgsr_softmax_max", _p(logits), N, C_, _p(ids), _p(score), ld, col, _p(ids_next))
+
+
+# ---- ASTER beam-search decode (csrc/aster.hip): R = N * B rows, row r = n * B + b ----------------------------------
+def aster_attention_rows(xproj, sproj, wv, bv, x, R, rows_per_seq, T, A, D, alpha, context):
+    """aster_attention on R decoder rows; row r reads xproj / x of sequence r // rows_per_seq"""
+    _launch("tpgsr_aster_attention_rows", _p(xproj), _p(sproj), _p(wv), _p(bv), _p(x), R, rows_per_seq, T, A, D, _p(alpha), _p(context))
+
+
+def beam_step(logits, seq, N, B, C_, eos, score_t, sym_t, pred_t):
+    """one beam-search step: seq [R] in/out; score_t / sym_t / pred_t [R] = one step of the [L][R] histories"""
+    _launch("tpgsr_beam_step", _p(logits), _p(seq), N, B, C_, int(eos), _p(score_t), _p(sym_t), _p(pred_t))
+
+
+def gather_rows(src, idx, R, W, dst):
+    _launch("tpgsr_gather_rows", _p(src), _p(idx), R, W, _p(dst))
+
+
+def beam_backtrack(score_hist, sym_hist, pred_hist, N, B, L, eos, ids_out, best_score, best_len):
+    _launch("tpgsr_beam_backtrack", _p(score_hist), _p(sym_hist), _p(pred_hist), N, B, L, int(eos), _p(ids_out), _p(best_score), _p(best_len))

@@ -1,11 +1,13 @@
 """RecognizerBuilder (reference: model/recognizer/recognizer_builder.py:27-104): the integrated ASTER recognizer.  Evaluation path with
-the greedy decoder: rectification (bilinear down-sample to 32x64 -> STN head -> TPS to 32x100), encoder, AttentionRecognitionHead.sample."""
+rectification (bilinear down-sample to 32x64 -> STN head -> TPS to 32x100), encoder, then AttentionRecognitionHead.sample (greedy, the
+default) or, with beam_width >= 1, AttentionRecognitionHead.beam_search: the decode the reference evaluates with (its beam_width is 5,
+recognizer_builder.py:24, :93)."""
 import torch
 from torch import nn
 
 from ... import functional as Fh
 from ..tps_spatial_transformer import TPSSpatialTransformer
-from .attention_recognition_head import AttentionRecognitionHead
+from .attention_recognition_head import MAX_BEAM_WIDTH, AttentionRecognitionHead
 from .resnet_aster import ResNet_ASTER
 from .stn_head import STNHead
 
@@ -16,8 +18,14 @@ tps_margins = [0.05, 0.05]
 
 
 class RecognizerBuilder(nn.Module):
-    def __init__(self, arch, rec_num_classes, sDim=512, attDim=512, max_len_labels=100, eos="EOS", STN_ON=True):
+    def __init__(self, arch, rec_num_classes, sDim=512, attDim=512, max_len_labels=100, eos="EOS", STN_ON=True, beam_width=0):
         super().__init__()
+        if isinstance(beam_width, bool) or not isinstance(beam_width, int) or not 0 <= beam_width <= MAX_BEAM_WIDTH:
+            raise ValueError(f"RecognizerBuilder: beam_width must be 0 (greedy decode) or an integer in 1..{MAX_BEAM_WIDTH} (got {beam_width!r})")
+        if beam_width >= 1 and (isinstance(eos, bool) or not isinstance(eos, int)):
+            raise ValueError(f"RecognizerBuilder: the beam-search decode needs the integer class id of the end-of-sequence symbol, "
+                             f"eos=voc.index(\"EOS\") (got eos={eos!r})")
+        self.beam_width = beam_width
         self.arch, self.rec_num_classes, self.sDim, self.attDim = arch, rec_num_classes, sDim, attDim
         self.max_len_labels, self.eos, self.STN_ON = max_len_labels, eos, STN_ON
         self.tps_inputsize = tps_inputsize
@@ -38,7 +46,8 @@ class RecognizerBuilder(nn.Module):
 
     def forward(self, input_dict):
         """evaluation: {'images': (N, 3, 32, 128) in [-1, 1], ...} -> {'losses': {}, 'output': {'pred_rec', 'pred_rec_score'}} with the
-        GREEDY decode (the reference calls beam_search here, which raises on torch >= 1.5; its loss against dummy targets is not computed)"""
+        greedy decode (beam_width = 0) or the reference's beam search (beam_width >= 1: pred_rec_score is all ones, as the reference
+        returns it); the reference's loss against dummy targets is not computed"""
         if self.training:
             raise RuntimeError("RecognizerBuilder is an evaluation recognizer here (interfaces/base.py:831-842 loads it frozen); call .eval()")
         x = input_dict["images"] if isinstance(input_dict, dict) else input_dict
@@ -49,6 +58,9 @@ class RecognizerBuilder(nn.Module):
                 out["output"]["ctrl_points"], out["output"]["rectified_images"] = ctrl, x
             feats = self.encoder(x)
             out["output"]["encoder_feats"] = feats
-            ids, scores = self.decoder.sample([feats, None, None])
+            if self.beam_width >= 1:
+                ids, scores = self.decoder.beam_search(feats, self.beam_width, self.eos)
+            else:
+                ids, scores = self.decoder.sample([feats, None, None])
             out["output"]["pred_rec"], out["output"]["pred_rec_score"] = ids, scores
             return out
