@@ -21,40 +21,12 @@ sys.path.insert(0, ROOT)
 # launch carries (scalar arguments and the non-pointer fields of argument structs: the geometry the launcher derives its grid from).
 # Pointers are left out: they differ from run to run.
 SIGNATURE = r'''
-import ctypes as C, json, sys, zlib, torch
-sys.path.insert(0, %(root)r)
-from tpgsr_amd import kernels as K, _lib
+import json, sys, torch
+sys.path[:0] = [%(root)r, %(tests)r]
+from tpgsr_amd import kernels as K
 assert K.DRYRUN
 from tpgsr_amd.model import tsrn
-
-def fields(obj, out):
-    for name, t in obj._fields_:
-        v = getattr(obj, name)
-        if isinstance(v, C.Structure):
-            fields(v, out)
-        elif t in (_lib.ci, _lib.ll, _lib.cf):
-            out.append((name, round(float(v), 6)))
-
-def signature(net):
-    lines = []
-    for key, pl in net._engine()._plans.items():
-        for pname in ("pack", "pre", "fwd", "bwd"):
-            plan = pl[pname]
-            if len(plan):
-                plan.run()                              # the native executor checks entry point and argument count
-            for name, fn, args, sid in plan.ops:
-                vals = []
-                if fn is None:
-                    vals.append(args)
-                else:
-                    for t, a in zip(fn.argtypes, args):
-                        if t in (_lib.ci, _lib.ll, _lib.cf):
-                            vals.append(round(float(a), 6))
-                        elif t is not _lib.vp:
-                            fields(a._obj, vals)
-                crc = zlib.crc32(repr(vals).encode())
-                lines.append("%%s %%s %%s %%d %%08x" %% ("/".join(str(k) for k in key), pname, name, sid, crc))
-    return lines
+from plan_signature import signature              # (a TSRN entry lists its plans as pack, pre, fwd, bwd)
 
 def record(hidden, tl, stn, N):
     torch.manual_seed(0)
@@ -68,7 +40,7 @@ def record(hidden, tl, stn, N):
     with torch.no_grad():
         z = net(x, *extra)
     assert tuple(y.shape) == tuple(z.shape) == (N, 4, 32, 128)
-    return signature(net)
+    return signature(net._engine()._plans)
 
 print("RESULT " + json.dumps({"tl": record(%(hidden)d, True, True, 4), "plain": record(%(hidden)d, False, False, 2)}))
 '''
@@ -78,7 +50,7 @@ def _signature(hidden):
     env = dict(os.environ, TPGSR_PLAN_DRYRUN="1")
     for k in [k for k in env if k.startswith("TPGSR_") and k != "TPGSR_PLAN_DRYRUN"]:
         del env[k]                                      # the recorded schedule is the default one
-    r = subprocess.run([sys.executable, "-c", SIGNATURE % dict(root=ROOT, hidden=hidden)], capture_output=True, text=True, env=env, timeout=550)
+    r = subprocess.run([sys.executable, "-c", SIGNATURE % dict(root=ROOT, tests=os.path.join(ROOT, "tests"), hidden=hidden)], capture_output=True, text=True, env=env, timeout=550)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
 

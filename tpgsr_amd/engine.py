@@ -880,11 +880,10 @@ class TSRNEngine(_EngineBase):
                               lambda ws, final: self._record(N, H, W, training, ws, final, bool(defer_join)))
 
     def _record(self, N, H, W, training, ws, final, defer_join=False):
-        pre, fwd, bwd, pack = Plan("tsrn_fwd_pre"), Plan("tsrn_fwd"), Plan("tsrn_bwd"), Plan("tsrn_pack")
+        pre, fwd, pack = Plan("tsrn_fwd_pre"), Plan("tsrn_fwd"), Plan("tsrn_pack")
+        bwd = K.backward_plan("tsrn_bwd", overlap=self.overlap_wgrad, defer=self.defer_reduce,
+                              use_leaf=self.leaf_stn and self.overlap_wgrad and self.defer_reduce)
         pre.final = fwd.final = bwd.final = pack.final = final
-        bwd.overlap = self.overlap_wgrad
-        bwd.deferred = [] if self.defer_reduce else None
-        bwd.use_leaf = self.leaf_stn and self.overlap_wgrad and self.defer_reduce
         self._cur_ws, self._wg_idx, self._compose = ws, 0, []
         for bn in self._bn_layers:
             bn.use(ws)

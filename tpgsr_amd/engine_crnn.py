@@ -259,15 +259,13 @@ class CRNNEngine(_EngineBase):
         return self._two_pass((N, bool(training), slot, getattr(self, "role", "tpg"), K.POLICY), lambda ws, final: self._record(N, training, ws, final))
 
     def _record(self, N, training, ws, final):
-        fwd, bwd, bwd_b, dgp, pack = Plan("crnn_fwd"), Plan("crnn_bwd"), Plan("crnn_bwd_b"), Plan("crnn_dgray"), Plan("crnn_pack")
+        fwd, dgp, pack = Plan("crnn_fwd"), Plan("crnn_dgray"), Plan("crnn_pack")
         fwd_b, pack_late = Plan("crnn_fwd_b"), Plan("crnn_pack_late")
-        fwd.final = bwd.final = bwd_b.final = dgp.final = pack.final = fwd_b.final = pack_late.final = final
-        split_pack = training and os.environ.get("TPGSR_CRNN_PACK_SPLIT", "1") != "0"
         # weight gradients on the side stream + one batched slab reduce, as in TSRNEngine (every buffer a weight-gradient
         # launch reads -- ds{i}, saved activations, the LSTM gate gradients after the time loop -- is written once per pass)
-        bwd.overlap = bwd_b.overlap = os.environ.get("TPGSR_OVERLAP_WGRAD", "1") != "0"
-        defer = os.environ.get("TPGSR_DEFER_REDUCE", "1") != "0"
-        bwd.deferred, bwd_b.deferred = ([] if defer else None), ([] if defer else None)
+        bwd, bwd_b = K.backward_plan("crnn_bwd"), K.backward_plan("crnn_bwd_b")
+        fwd.final = bwd.final = bwd_b.final = dgp.final = pack.final = fwd_b.final = pack_late.final = final
+        split_pack = training and os.environ.get("TPGSR_CRNN_PACK_SPLIT", "1") != "0"
         self._cur_ws, self._wg_idx = ws, 0
         for bn in self._bn_layers:
             bn.use(ws)
@@ -285,7 +283,7 @@ class CRNNEngine(_EngineBase):
                 # parameter arena (both BiLSTMs, conv6..conv3, bn6 / bn4: 95.6 % of it) is final there, and a data-parallel train step
                 # launches that bucket's all-reduce between the two (backward(..., after_early=...)) under the rest of the pass
                 self._record_bwd(N, ws, cut_to=bwd_b if os.environ.get("TPGSR_CRNN_BWD_SPLIT", "1") != "0" else None)
-                if defer:
+                if K.deferring():
                     K.flush_wgrad_reduces()
                 K._REC.join()
             with recording(dgp), K.conv_terms(K.terms_for("tpg", "bwd")):   # d gray: only later cascade stages ask for it

@@ -21,7 +21,9 @@ Two ways to run it:
   `.grad` views).
 
 `FunctionalSREngine` (below) is the same adapter on the SR-network side of the protocol, for the `_TL` baseline backbones of the cascade loop
-(`TPGSR_SR_RECORD=0` switches ITS recording off); `PlainSREngine` is that adapter for the prior-free baselines (SRResNet / RDN / VDSR)."""
+(`TPGSR_SR_RECORD=0` switches ITS recording off); `PlainSREngine` is that adapter for the prior-free baselines (SRResNet / RDN / VDSR).
+The trace (`FunctionalEngine._trace`) and the two replays (`_replay_forward` / `_replay_backward`) exist once: a subclass names its static
+inputs, its plans and its output, and keeps the operator-by-operator mode of its own `forward` / `backward`."""
 import os
 from typing import Dict, Optional
 
@@ -36,13 +38,17 @@ from .kernels import Plan, recording
 class FunctionalEngine:
     FUSED = False        # no fused autograd node: tpgsr_amd.distributed.DataParallel hooks the parameters instead
     T, IMG_HW = 26, (32, 100)
+    # what a recorded plan dictionary of this engine holds next to the static inputs (_static_inputs):
+    PLAN_NAMES = ("opt_fwd", "opt_bwd")
+    OUT, DOUT = "logits", "dlogits"      # the recorded output and the buffer its incoming gradient is copied into
+    GRAD_OF = ("gray", "dgray")          # the static input whose gradient the backward plan leaves behind, and under which key (None: none)
 
     def __init__(self, module: torch.nn.Module):
         self.module = module
         self.arena = ParamArena(module)
         self.device = None
         self.record = os.environ.get("TPGSR_OPT_RECORD", "1") != "0"
-        self._plans: Dict[tuple, dict] = {}      # (N, training, slot, role) -> recorded plans + their static buffers
+        self._plans: Dict[tuple, dict] = {}      # _key() -> recorded plans + their static buffers
         self._saved: Dict[int, tuple] = {}
         self._pending_batches = 0
         self._kernel_writes = 0      # bumped by FusedAdam / broadcasts (engine protocol); every plan here re-packs its weights per replay
@@ -69,54 +75,102 @@ class FunctionalEngine:
                     b += self._pending_batches
         self._pending_batches = 0
 
+    def _check_mode(self, training):
+        if bool(self.module.training) != bool(training):
+            raise RuntimeError(f"{type(self.module).__name__}: forward(training={training}) on a module in "
+                               f"{'train' if self.module.training else 'eval'}() mode")
+
+    def _pop_saved(self, slot):
+        if slot not in self._saved:
+            raise RuntimeError(f"{type(self.module).__name__}: backward without a training-mode forward in slot {slot}")
+        return self._saved.pop(slot)
+
+    # ---- what a subclass describes --------------------------------------------------------------------------------------------------
+    def _static_inputs(self, shape) -> dict:
+        """the plan's input buffers, in the order the module takes them (shape: the first input's)"""
+        return dict(gray=torch.empty(shape[0], 1, *self.IMG_HW, device=self.device))
+
+    def _key(self, shape, training, slot, role) -> tuple:
+        return (shape[0], bool(training), slot, role, K.POLICY)
+
+    def _output(self, y):
+        return y.permute(1, 0, 2)                        # [N][T][C]: the contiguous tensor the prediction layer wrote
+
+    def _input_grad(self, got):
+        return got[0] if got else None
+
     # ---- recorded mode ------------------------------------------------------------------------------------------------------------
-    def plans(self, N: int, training: bool, slot: int = 0) -> dict:
+    def _plans_for(self, shape, training: bool, slot: int = 0) -> dict:
         role = getattr(self, "role", "tpg")
-        key = (N, bool(training), slot, role, K.POLICY)
+        key = self._key(tuple(shape), training, slot, role)
         pl = self._plans.get(key)
         if pl is None:
-            pl = self._plans[key] = self._trace(N, training, role)
+            pl = self._plans[key] = self._trace(tuple(shape), training, role)
         return pl
 
-    def _trace(self, N, training, role):
-        dev = self.device
-        gray = torch.empty(N, 1, *self.IMG_HW, device=dev)
-        fwd = Plan("opt_fwd")
-        out = dict(fwd=fwd, gray=gray)
-        with recording(fwd), K.conv_terms(K.terms_for(role, "fwd")):
-            if training:
-                x = gray.requires_grad_(True)
-                with torch.enable_grad():
-                    y = self.module(x)
-            else:
-                with torch.no_grad():
-                    y = self.module(gray)
-        logits = y.permute(1, 0, 2)                      # [N][T][C]: the contiguous tensor the prediction layer wrote
-        assert logits.is_contiguous() and logits.shape[0] == N
-        out["logits"] = logits
+    def _trace(self, shape, training, role):
+        ins = self._static_inputs(shape)
+        fwd = Plan(self.PLAN_NAMES[0])
+        out = dict(fwd=fwd, **ins)
+        x = ins[self.GRAD_OF[0]].requires_grad_(True) if training and self.GRAD_OF else None     # (the static buffer itself)
+        with recording(fwd), K.conv_terms(K.terms_for(role, "fwd")), (torch.enable_grad() if training else torch.no_grad()):
+            y = self.module(*ins.values())
+        res = self._output(y)
+        assert res.is_contiguous() and res.shape[0] == shape[0]
+        out[self.OUT] = res.detach()
         if not training:
             return out
-        bwd = Plan("opt_bwd")
-        bwd.overlap = os.environ.get("TPGSR_OVERLAP_WGRAD", "1") != "0"
-        bwd.deferred = [] if os.environ.get("TPGSR_DEFER_REDUCE", "1") != "0" else None
-        dlogits = torch.empty_like(logits)
+        bwd = K.backward_plan(self.PLAN_NAMES[1])
+        dres = torch.empty_like(out[self.OUT])
         self.arena.attach_grads()
         grads = {p.data_ptr(): p.grad for p in self.module.parameters() if p.requires_grad}
         got = []
-        h = x.register_hook(lambda g_: got.append(g_))
+        h = x.register_hook(got.append) if x is not None else None
         prev, Fh.GRAD_SINK = Fh.GRAD_SINK, grads
         try:
-            with recording(bwd), K.conv_terms(K.terms_for("tpg", "bwd")):
-                torch.autograd.backward(logits, dlogits)
+            # terms_for(role, "bwd"): for the recogniser the number "tpg" gives -- terms_for maps "teacher" to "tpg" outside the x2 policy
+            # and returns 2 for either inside it
+            with recording(bwd), K.conv_terms(K.terms_for(role, "bwd")):
+                torch.autograd.backward(res, dres)
                 if bwd.deferred is not None:
                     K.flush_wgrad_reduces()
                 K._REC.join()
         finally:
             Fh.GRAD_SINK = prev
-            h.remove()
-        x.grad = None                                     # (assigned by autograd at trace time; the hook's tensor is the live one)
-        out.update(bwd=bwd, dlogits=dlogits, dgray=got[0] if got else None, graph=y)     # `graph` keeps the saved activations alive
+            if h is not None:
+                h.remove()
+        out.update({"bwd": bwd, self.DOUT: dres})
+        if x is not None:
+            x.grad = None                                 # (assigned by autograd at trace time; the hook's tensor is the live one)
+            out[self.GRAD_OF[1]] = self._input_grad(got)
+        out["graph"] = y                                  # keeps the saved activations alive
         return out
+
+    def _replay_forward(self, ins: dict, training, slot) -> torch.Tensor:
+        """ins: the tensors for _static_inputs' buffers, in their order (None: zeros)"""
+        first = next(iter(ins.values()))
+        pl = self._plans_for(first.shape, training, slot)
+        for name, t in ins.items():
+            if t is None:
+                K.zero(pl[name], pl[name].numel())
+            else:
+                K.copy(t.contiguous(), pl[name], t.numel())
+        pl["fwd"].run()
+        if training:
+            self._pending_batches += 1
+            self._saved[slot] = (first.shape[0], pl)
+        res = torch.empty_like(pl[self.OUT])
+        K.copy(pl[self.OUT], res, res.numel())
+        return res
+
+    def _replay_backward(self, N, dout, slot) -> dict:
+        """-> the slot's plan dictionary, its backward plan replayed on `dout`"""
+        n, pl = self._pop_saved(slot)
+        assert n == N
+        self.arena.attach_grads()                       # (same addresses as at trace time: the arena does not move)
+        K.copy(dout.contiguous(), pl[self.DOUT], pl[self.DOUT].numel())
+        pl["bwd"].run()
+        return pl
 
     # ---- the engine protocol --------------------------------------------------------------------------------------------------------
     def forward(self, gray: torch.Tensor, training: bool, slot: int = 0, late_stream=None, after_late=None) -> torch.Tensor:
@@ -124,21 +178,10 @@ class FunctionalEngine:
         protocol -- nothing is packed apart here, the callback runs first)"""
         if after_late is not None:
             after_late()
-        if bool(self.module.training) != bool(training):
-            raise RuntimeError(f"{type(self.module).__name__}: forward(training={training}) on a module in "
-                               f"{'train' if self.module.training else 'eval'}() mode")
+        self._check_mode(training)
         self.bind(gray.device)
         if self.record:
-            N = gray.shape[0]
-            pl = self.plans(N, training, slot)
-            K.copy(gray.contiguous(), pl["gray"], gray.numel())
-            pl["fwd"].run()
-            if training:
-                self._pending_batches += 1
-                self._saved[slot] = (N, pl)
-            res = torch.empty_like(pl["logits"])
-            K.copy(pl["logits"], res, res.numel())
-            return res
+            return self._replay_forward(dict(gray=gray), training, slot)
         if not training:
             with torch.no_grad():
                 y = self.module(gray)                     # (T, N, C), a permuted view of the contiguous [N][T][C] result
@@ -151,20 +194,14 @@ class FunctionalEngine:
         return logits.detach().contiguous()
 
     def backward(self, N: int, gray: torch.Tensor, dlogits: torch.Tensor, need_dgray: bool = False, slot: int = 0) -> Optional[torch.Tensor]:
-        if slot not in self._saved:
-            raise RuntimeError(f"{type(self.module).__name__}: backward without a training-mode forward in slot {slot}")
         if self.record:
-            n, pl = self._saved.pop(slot)
-            assert n == N
-            self.arena.attach_grads()                       # (same addresses as at trace time: the arena does not move)
-            K.copy(dlogits.contiguous(), pl["dlogits"], pl["dlogits"].numel())
-            pl["bwd"].run()
+            pl = self._replay_backward(N, dlogits, slot)
             if not need_dgray:
                 return None
             res = torch.empty_like(pl["dgray"])
             K.copy(pl["dgray"], res, res.numel())
             return res
-        x, logits = self._saved.pop(slot)
+        x, logits = self._pop_saved(slot)
         self.arena.attach_grads()
         torch.autograd.backward(logits, dlogits.reshape(logits.shape))
         return x.grad if need_dgray else None
@@ -177,80 +214,40 @@ class FunctionalSREngine(FunctionalEngine):
     `TPGSRTrainStep`, `FusedAdam`, `ArenaPool` and `TextSREvaluator` drive the module through this adapter; `module(x, prior)` under
     autograd keeps working on its own.
 
-    RECORDED (default, `TPGSR_SR_RECORD=0` switches it off): one trace per (N, H, W, training, slot, policy) -- the slot keeps the saved
-    activations of each cascade stage apart: a shared SR net runs `stu_iter` forward passes before any backward pass.  A forward and a
-    backward pass are one replay each: parameter gradients go through `functional.GRAD_SINK` into the arena, weight gradients run on the
-    weight-gradient stream with one batched slab reduce, every multi-consumer tensor of the module's forward is a `functional.fork`.
-    Otherwise operator by operator through autograd: the reference implementation of the recorded mode."""
-    FUSED = False
+    RECORDED (default, `TPGSR_SR_RECORD=0` switches it off): one trace (`FunctionalEngine._trace`) per (N, H, W, training, slot, policy)
+    -- the slot keeps the saved activations of each cascade stage apart: a shared SR net runs `stu_iter` forward passes before any
+    backward pass.  A forward and a backward pass are one replay each: parameter gradients go through `functional.GRAD_SINK` into the
+    arena, weight gradients run on the weight-gradient stream with one batched slab reduce, every multi-consumer tensor of the module's
+    forward is a `functional.fork`.  Otherwise operator by operator through autograd: the reference implementation of the recorded mode."""
     role = "sr"
     scale = 2            # SR grid / LR grid: the operator-level backbones are built for the reference's x2 only (DESIGN section 7)
+    PLAN_NAMES = ("sr_tl_fwd", "sr_tl_bwd")
+    OUT, DOUT = "sr", "dsr"
+    GRAD_OF = ("prior", "dprior")
 
     def __init__(self, module: torch.nn.Module):
         super().__init__(module)
         self.record = os.environ.get("TPGSR_SR_RECORD", "1") != "0"
 
-    # ---- recorded mode ------------------------------------------------------------------------------------------------------------
-    def sr_plans(self, shape, training: bool, slot: int = 0) -> dict:
-        key = (tuple(shape), bool(training), slot, K.POLICY)
-        pl = self._plans.get(key)
-        if pl is None:
-            pl = self._plans[key] = self._trace_sr(tuple(shape), training)
-        return pl
+    def _static_inputs(self, shape) -> dict:
+        return dict(lr=torch.empty(*shape, device=self.device), prior=torch.empty(shape[0], 37, 1, 26, device=self.device))
 
-    def _trace_sr(self, shape, training):
-        dev = self.device
-        N = shape[0]
-        lr = torch.empty(*shape, device=dev)
-        prior = torch.empty(N, 37, 1, 26, device=dev)
-        fwd = Plan("sr_tl_fwd")
-        out = dict(fwd=fwd, lr=lr, prior=prior)
-        with recording(fwd), K.conv_terms(K.terms_for("sr", "fwd")):
-            if training:
-                t = prior.requires_grad_(True)
-                with torch.enable_grad():
-                    y = self.module(lr, t)
-            else:
-                with torch.no_grad():
-                    y = self.module(lr, prior)
-        assert y.is_contiguous() and y.shape[0] == N
-        out["sr"] = y.detach()
-        if not training:
-            return out
-        bwd = Plan("sr_tl_bwd")
-        bwd.overlap = os.environ.get("TPGSR_OVERLAP_WGRAD", "1") != "0"
-        bwd.deferred = [] if os.environ.get("TPGSR_DEFER_REDUCE", "1") != "0" else None
-        dsr = torch.empty_like(out["sr"])
-        self.arena.attach_grads()
-        grads = {p.data_ptr(): p.grad for p in self.module.parameters() if p.requires_grad}
-        got = []
-        h = t.register_hook(lambda g_: got.append(g_))
-        prev, Fh.GRAD_SINK = Fh.GRAD_SINK, grads
-        try:
-            with recording(bwd), K.conv_terms(K.terms_for("sr", "bwd")):
-                torch.autograd.backward(y, dsr)
-                if bwd.deferred is not None:
-                    K.flush_wgrad_reduces()
-                K._REC.join()
-        finally:
-            Fh.GRAD_SINK = prev
-            h.remove()
-        t.grad = None
+    def _key(self, shape, training, slot, role) -> tuple:
+        return (shape, bool(training), slot, K.POLICY)
+
+    def _output(self, y):
+        return y
+
+    def _input_grad(self, got):
         if not got or not got[0].is_contiguous():
             raise RuntimeError(f"{type(self.module).__name__}: the traced backward pass produced no contiguous text-prior gradient")
-        out.update(bwd=bwd, dsr=dsr, dprior=got[0], graph=y)       # `graph` keeps the saved activations alive
-        return out
+        return got[0]
 
     # ---- the engine protocol --------------------------------------------------------------------------------------------------------
     def forward_pre(self, lr, training, slot: int = 0, defer_join: bool = False):
         """engine protocol: the prior-independent prologue `TSRNEngine` runs next to the text-prior generator.  Nothing here is worth
         splitting out (the first conv of these backbones is a fraction of a percent of the pass): a no-op"""
         return None
-
-    def _check_mode(self, training):
-        if bool(self.module.training) != bool(training):
-            raise RuntimeError(f"{type(self.module).__name__}: forward(training={training}) on a module in "
-                               f"{'train' if self.module.training else 'eval'}() mode")
 
     def forward(self, lr, training, prior=None, slot: int = 0, defer_join: bool = False, pre_done: bool = False) -> torch.Tensor:
         """lr (N, C, H, W), prior (N, 37, 1, 26) or None (zeros) -> SR image (N, C, 2H, 2W)"""
@@ -260,19 +257,7 @@ class FunctionalSREngine(FunctionalEngine):
         if prior is not None and tuple(prior.shape) != (N, 37, 1, 26):
             raise ValueError(f"{type(self.module).__name__}: the text prior is (N, 37, 1, 26), got {tuple(prior.shape)}")
         if self.record:
-            pl = self.sr_plans(lr.shape, training, slot)
-            K.copy(lr.contiguous(), pl["lr"], lr.numel())
-            if prior is None:
-                K.zero(pl["prior"], pl["prior"].numel())
-            else:
-                K.copy(prior.contiguous(), pl["prior"], prior.numel())
-            pl["fwd"].run()
-            if training:
-                self._pending_batches += 1
-                self._saved[slot] = (N, pl)
-            res = torch.empty_like(pl["sr"])
-            K.copy(pl["sr"], res, res.numel())
-            return res
+            return self._replay_forward(dict(lr=lr, prior=prior), training, slot)
         with K.conv_terms(K.terms_for("sr", "fwd")):
             if not training:
                 with torch.no_grad():
@@ -285,21 +270,13 @@ class FunctionalSREngine(FunctionalEngine):
 
     def backward(self, x_shape, sr, dsr, slot: int = 0, defer_join: bool = False) -> torch.Tensor:
         """d loss / d SR image -> d loss / d prior (N, 37, 1, 26); parameter gradients are accumulated into the arena"""
-        if slot not in self._saved:
-            raise RuntimeError(f"{type(self.module).__name__}: backward without a training-mode forward in slot {slot}")
         if self.record:
-            n, pl = self._saved.pop(slot)
-            assert n == x_shape[0]
-            self.arena.attach_grads()                       # (same addresses as at trace time: the arena does not move)
-            K.copy(dsr.contiguous(), pl["dsr"], pl["dsr"].numel())
-            pl["bwd"].run()
-            return pl["dprior"]        # the plan's buffer of this slot: valid until the slot's next backward pass
-        t, y = self._saved.pop(slot)
+            return self._replay_backward(x_shape[0], dsr, slot)["dprior"]    # the plan's buffer of this slot: valid until the slot's next backward pass
+        t, y = self._pop_saved(slot)
         self.arena.attach_grads()
         with K.conv_terms(K.terms_for("sr", "bwd")):
             torch.autograd.backward(y, dsr.reshape(y.shape))
         return t.grad.contiguous()
-
 
 
 class PlainSREngine(FunctionalSREngine):
@@ -312,41 +289,11 @@ class PlainSREngine(FunctionalSREngine):
     policy) into a forward and a backward plan -- parameter gradients through `functional.GRAD_SINK` into the arena, weight gradients on
     the weight-gradient stream with one batched slab reduce; otherwise operator by operator through autograd.  The input image needs no
     gradient, so the first layer's data gradient is never launched, and `backward` returns nothing."""
+    PLAN_NAMES = ("sr_plain_fwd", "sr_plain_bwd")
+    GRAD_OF = None
 
-    def _trace_sr(self, shape, training):
-        dev = self.device
-        N = shape[0]
-        lr = torch.empty(*shape, device=dev)
-        fwd = Plan("sr_plain_fwd")
-        out = dict(fwd=fwd, lr=lr)
-        with recording(fwd), K.conv_terms(K.terms_for("sr", "fwd")):
-            if training:
-                with torch.enable_grad():
-                    y = self.module(lr)
-            else:
-                with torch.no_grad():
-                    y = self.module(lr)
-        assert y.is_contiguous() and y.shape[0] == N
-        out["sr"] = y.detach()
-        if not training:
-            return out
-        bwd = Plan("sr_plain_bwd")
-        bwd.overlap = os.environ.get("TPGSR_OVERLAP_WGRAD", "1") != "0"
-        bwd.deferred = [] if os.environ.get("TPGSR_DEFER_REDUCE", "1") != "0" else None
-        dsr = torch.empty_like(out["sr"])
-        self.arena.attach_grads()
-        grads = {p.data_ptr(): p.grad for p in self.module.parameters() if p.requires_grad}
-        prev, Fh.GRAD_SINK = Fh.GRAD_SINK, grads
-        try:
-            with recording(bwd), K.conv_terms(K.terms_for("sr", "bwd")):
-                torch.autograd.backward(y, dsr)
-                if bwd.deferred is not None:
-                    K.flush_wgrad_reduces()
-                K._REC.join()
-        finally:
-            Fh.GRAD_SINK = prev
-        out.update(bwd=bwd, dsr=dsr, graph=y)       # `graph` keeps the saved activations alive
-        return out
+    def _static_inputs(self, shape) -> dict:
+        return dict(lr=torch.empty(*shape, device=self.device))
 
     def forward(self, lr, training, prior=None, slot: int = 0, defer_join: bool = False, pre_done: bool = False) -> torch.Tensor:
         """lr (N, C, H, W) -> SR image (N, C, 2H, 2W)"""
@@ -355,15 +302,7 @@ class PlainSREngine(FunctionalSREngine):
         self._check_mode(training)
         self.bind(lr.device)
         if self.record:
-            pl = self.sr_plans(lr.shape, training, slot)
-            K.copy(lr.contiguous(), pl["lr"], lr.numel())
-            pl["fwd"].run()
-            if training:
-                self._pending_batches += 1
-                self._saved[slot] = (lr.shape[0], pl)
-            res = torch.empty_like(pl["sr"])
-            K.copy(pl["sr"], res, res.numel())
-            return res
+            return self._replay_forward(dict(lr=lr), training, slot)
         with K.conv_terms(K.terms_for("sr", "fwd")):
             if not training:
                 with torch.no_grad():
@@ -375,16 +314,10 @@ class PlainSREngine(FunctionalSREngine):
 
     def backward(self, x_shape, sr, dsr, slot: int = 0, defer_join: bool = False) -> None:
         """d loss / d SR image -> parameter gradients, accumulated into the arena (there is no prior to return a gradient for)"""
-        if slot not in self._saved:
-            raise RuntimeError(f"{type(self.module).__name__}: backward without a training-mode forward in slot {slot}")
         if self.record:
-            n, pl = self._saved.pop(slot)
-            assert n == x_shape[0]
-            self.arena.attach_grads()                       # (same addresses as at trace time: the arena does not move)
-            K.copy(dsr.contiguous(), pl["dsr"], pl["dsr"].numel())
-            pl["bwd"].run()
+            self._replay_backward(x_shape[0], dsr, slot)
             return None
-        _, y = self._saved.pop(slot)
+        _, y = self._pop_saved(slot)
         self.arena.attach_grads()
         with K.conv_terms(K.terms_for("sr", "bwd")):
             torch.autograd.backward(y, dsr.reshape(y.shape))

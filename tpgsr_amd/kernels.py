@@ -284,6 +284,10 @@ class Plan:
         self.forks = 0
         self.leaf_pending = False   # launches on the leaf stream nothing has been ordered after yet
         self.hold = None            # side_batch(): side-stream launches held back until the batch closes [(op, [(key, arg index)])]
+        # scheduling flags of a backward plan (backward_plan() sets them; every other plan records serially)
+        self.overlap = False        # weight-gradient launches go to the side stream (side())
+        self.deferred = None        # a list: the weight-gradient slab reduces are collected here, ONE launch by flush_wgrad_reduces()
+        self.use_leaf = False       # leaf() sections go to the third stream (needs overlap)
         self._native = None  # tpgsr_plan handle, built on first run()
         self._has_side = False
         self._has_leaf = False
@@ -427,6 +431,17 @@ class Plan:
         return len(self.ops)
 
 
+def backward_plan(name, overlap=None, defer=None, use_leaf=False) -> Plan:
+    """A Plan for a backward pass, with its scheduling flags (Plan.overlap / deferred / use_leaf).  overlap / defer None: what
+    TPGSR_OVERLAP_WGRAD / TPGSR_DEFER_REDUCE say NOW (default on) -- the only place that reads the two variables for a plan."""
+    plan = Plan(name)
+    plan.overlap = os.environ.get("TPGSR_OVERLAP_WGRAD", "1") != "0" if overlap is None else bool(overlap)
+    defer = os.environ.get("TPGSR_DEFER_REDUCE", "1") != "0" if defer is None else defer
+    plan.deferred = [] if defer else None
+    plan.use_leaf = bool(use_leaf)
+    return plan
+
+
 class _SideCtx:
     def __init__(self, plan):
         self.plan = plan
@@ -471,7 +486,7 @@ class _NoSide:
 def side():
     """Side-stream section of the plan being recorded (no-op when launching eagerly outside a plan, and inside a leaf section:
     the leaf stream runs its own weight gradients in order)."""
-    return _REC.side() if _REC is not None and getattr(_REC, "overlap", False) and _REC.sid != 2 else _NoSide()
+    return _REC.side() if _REC is not None and _REC.overlap and _REC.sid != 2 else _NoSide()
 
 
 SIDE_BATCH = os.environ.get("TPGSR_SIDE_BATCH", "1") != "0"
@@ -479,7 +494,7 @@ SIDE_BATCH = os.environ.get("TPGSR_SIDE_BATCH", "1") != "0"
 
 def side_batch_begin():
     """see Plan.side_batch_begin (no-op outside a recording with side streams, and with TPGSR_SIDE_BATCH=0)"""
-    if SIDE_BATCH and _REC is not None and getattr(_REC, "overlap", False) and _REC.sid == 0 and _REC.hold is None:
+    if SIDE_BATCH and _REC is not None and _REC.overlap and _REC.sid == 0 and _REC.hold is None:
         _REC.side_batch_begin()
         return True
     return False
@@ -492,7 +507,7 @@ def side_batch_end(opened: bool):
 
 def leaf():
     """Leaf-stream section of the plan being recorded (Plan.leaf); no-op unless the plan opted in (`use_leaf`)."""
-    return _REC.leaf() if _REC is not None and getattr(_REC, "overlap", False) and getattr(_REC, "use_leaf", False) else _NoSide()
+    return _REC.leaf() if _REC is not None and _REC.overlap and _REC.use_leaf else _NoSide()
 
 
 def leaf_join():
@@ -537,7 +552,7 @@ def continue_in(plan: Plan):
     plan's launches follow it in stream order, and its join covers both."""
     global _REC
     assert _REC is not None and _REC.sid == 0 and _REC.hold is None, "continue_in inside a stream section / side batch"
-    assert not getattr(_REC, "deferred", None), "deferred slab reduces must be flushed before the recording moves on"
+    assert not _REC.deferred, "deferred slab reduces must be flushed before the recording moves on"
     if _REC.forks or _REC.leaf_pending:
         plan.forks += 1            # something of the first plan may still run on the side stream: the second plan's join must be emitted
     _REC = plan
@@ -818,7 +833,7 @@ def conv_wgrad_batch(wargs):
 
 def deferring() -> bool:
     """True while recording a plan that batches its weight-gradient slab reduces into one launch (Plan.deferred)."""
-    return _REC is not None and getattr(_REC, "deferred", None) is not None
+    return _REC is not None and _REC.deferred is not None
 
 
 def wgrad_reduce(part, dbpart, Z, g: ConvGeom, dw, db=None, *, layout=0, accumulate=True, gscale=1.0, real=None):
