@@ -433,6 +433,9 @@ int tpgsr_affine_act_pool_bwd(const float* x, const float* dout, int N, int H, i
 int tpgsr_prelu_fwd(const float* x, const float* alpha, long long n, float* y, void* stream);
 int tpgsr_prelu_bwd(const float* x, const float* alpha, const float* dy, const float* dy2, long long n, float* dx,
                     float* dalpha_partial, int nblk, void* stream);
+/* nn.LeakyReLU(slope), any n: y = x > 0 ? x : x * slope; dx = x > 0 ? dy : dy * slope (derivative `slope` at x <= 0, as ATen's) */
+int tpgsr_leaky_relu_fwd(const float* x, long long n, float slope, float* y, void* stream);
+int tpgsr_leaky_relu_bwd(const float* x, const float* dy, long long n, float slope, float* dx, void* stream);
 /* out = a + b (b optional scale) ; out = a*mish'(x) etc. */
 int tpgsr_add(const float* a, const float* b, long long n, float* out, void* stream);
 /* out = ((a0 + a1) + a2) + ... + a[k-1], 2 <= k <= 8 addends of n floats (a[k..7] ignored): one launch, fixed left-to-right fp32 order
@@ -648,6 +651,23 @@ int tpgsr_hreduce(const float* in, int N, int H, int W, int C, float scale, floa
 int tpgsr_hbroadcast(const float* dout, int N, int H, int W, int C, float scale, float* din, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * nn.ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1, bias=False) (model/lapsrn.py:48, :64), NHWC, w [Cin][Cout][4][4].
+ * Sub-pixel form: the layer equals a 3x3 pad-1 convolution to 4 Cout channels (channel co*4 + a*2 + b = output phase (a, b); tap (r, s)
+ * holds w[a - 2r + 3][b - 2s + 3] where that index exists, 0 elsewhere) + PixelShuffle(2) -- tpgsr_conv_fwd with out_ps.  _expand gathers
+ * w into w3 [4 Cout][Cin][3][3]; _fold_grad gathers that convolution's weight gradient dW3 back into dw [Cin][Cout][4][4] (accumulate: +=).
+ * Pure gathers, one-to-one on the 16 live taps, bitwise reproducible.
+ * _small_*: direct kernels for 1 <= Cin, Cout <= 4 (anything else, or N H W >= 2^27, is refused before a launch), fixed summation
+ * order, no atomics.  _small_bwd_weight writes partial [nblk][Cin Cout 16] (workgroup b sums its run of input positions in order),
+ * finished by tpgsr_reduce_partials(partial, nblk, Cin Cout 16, dw, accumulate).
+ * ---------------------------------------------------------------------------------------------- */
+int tpgsr_tconv4s2_expand(const float* w, int Cin, int Cout, float* w3, void* stream);
+int tpgsr_tconv4s2_fold_grad(const float* dw3, int Cin, int Cout, float* dw, int accumulate, void* stream);
+int tpgsr_tconv4s2_small_fwd(const float* x, const float* w, int N, int H, int W, int Cin, int Cout, float* y, void* stream);
+int tpgsr_tconv4s2_small_bwd_data(const float* dy, const float* w, int N, int H, int W, int Cin, int Cout, float* dx, void* stream);
+int tpgsr_tconv4s2_small_bwd_weight(const float* x, const float* dy, int N, int H, int W, int Cin, int Cout, float* partial, int nblk,
+                                    void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Tail: out = tanh(bias + sum_kw P[h][w+kw-4][kw][co])  (model/tsrn.py:159,213), NCHW output
  * ---------------------------------------------------------------------------------------------- */
 int tpgsr_tail_shiftsum_tanh(const float* P, const float* bias, int N, int H, int W, int Co, int KS,
@@ -674,6 +694,12 @@ int tpgsr_image_loss_bwd(const float* out, const float* tgt, const float* dloss,
  * tpgsr_image_loss_finalize(partial, nblk, n, 0, w, 0, loss); bwd: dout = dloss[0] * w / n * sign(out - tgt), sign(0) = 0 */
 int tpgsr_l1_loss_fwd(const float* out, const float* tgt, long long n, float* partial, int nblk, void* stream);
 int tpgsr_l1_loss_bwd(const float* out, const float* tgt, const float* dloss, long long n, float w, float* dout, void* stream);
+/* L1_Charbonnier_loss (model/lapsrn.py:126-137): a SUM over n elements.  fwd: partial[b] = {sum sqrt((out - tgt)^2 + eps) of workgroup b, 0}
+ * in the same [nblk][2] rows, finished by tpgsr_image_loss_finalize(partial, nblk, 1, 0, w, 0, loss) (count 1: a sum, not a mean);
+ * bwd: dout = dloss[0] * w * d / sqrt(d^2 + eps), d = out - tgt */
+int tpgsr_charbonnier_loss_fwd(const float* out, const float* tgt, long long n, float eps, float* partial, int nblk, void* stream);
+int tpgsr_charbonnier_loss_bwd(const float* out, const float* tgt, const float* dloss, long long n, float eps, float w, float* dout,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Input pipeline (dataset/dataset.py:615-632 resizeNormalize, called by alignCollate_real* :1226-1323): Pillow's 8-bit

@@ -570,6 +570,41 @@ extern "C" int tpgsr_prelu_bwd(const float* x, const float* alpha, const float* 
   TPGSR_LAUNCH_CHECK("tpgsr_prelu_bwd");
 }
 
+// nn.LeakyReLU(slope) (the activation of LapSRN, model/lapsrn.py:29): y = x > 0 ? x : x * slope; dx = x > 0 ? dy : dy * slope (the derivative
+// at x <= 0 is `slope`, as ATen's).  Any n: 16-byte accesses while every pointer is 16-byte aligned (n4 groups), the rest element by element.
+__device__ __forceinline__ float leaky(float x, float v, float slope) { return x > 0.f ? v : v * slope; }
+
+__global__ __launch_bounds__(256) void leaky_relu_kernel(const float* __restrict__ x, const float* __restrict__ dy, long long n4, long long n,
+                                                         float slope, float* __restrict__ out) {
+  // dy == nullptr: the forward pass (out = leaky(x)); else the backward pass (out = dy scaled on the non-positive side of x)
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long long i = t0; i < n4; i += stride) {
+    const float4 v = ld4(x + i * 4), g = dy ? ld4(dy + i * 4) : v;
+    *reinterpret_cast<float4*>(out + i * 4) = make_float4(leaky(v.x, g.x, slope), leaky(v.y, g.y, slope), leaky(v.z, g.z, slope), leaky(v.w, g.w, slope));
+  }
+  for (long long i = n4 * 4 + t0; i < n; i += stride) out[i] = leaky(x[i], dy ? dy[i] : x[i], slope);
+}
+
+static int leaky_launch(const float* x, const float* dy, long long n, float slope, float* out, void* stream) {
+  const bool vec = ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)out)) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0, work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
+  const int grid = (int)max((long long)1, min((long long)4096, (work + 255) / 256));
+  hipLaunchKernelGGL(leaky_relu_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, dy, n4, n, slope, out);
+  return 0;
+}
+
+extern "C" int tpgsr_leaky_relu_fwd(const float* x, long long n, float slope, float* y, void* stream) {
+  TPGSR_CHECK_ARG(x && y && n > 0, "tpgsr_leaky_relu_fwd: bad arguments");
+  leaky_launch(x, nullptr, n, slope, y, stream);
+  TPGSR_LAUNCH_CHECK("tpgsr_leaky_relu_fwd");
+}
+
+extern "C" int tpgsr_leaky_relu_bwd(const float* x, const float* dy, long long n, float slope, float* dx, void* stream) {
+  TPGSR_CHECK_ARG(x && dy && dx && n > 0, "tpgsr_leaky_relu_bwd: bad arguments");
+  leaky_launch(x, dy, n, slope, dx, stream);
+  TPGSR_LAUNCH_CHECK("tpgsr_leaky_relu_bwd");
+}
+
 __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n4,
                                                   long long n, float* __restrict__ out) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {

@@ -339,6 +339,71 @@ extern "C" int tpgsr_l1_loss_bwd(const float* out, const float* tgt, const float
 }
 
 // ------------------------------------------------------------------------------------------------------
+// Charbonnier loss (L1_Charbonnier_loss, model/lapsrn.py:126-137: the image criterion of `--arch lapsrn`) -- a SUM over all elements
+//   forward : partial[b][0] = sum sqrt(d^2 + eps), d = out - tgt, over workgroup b's elements (fp64 inside the workgroup), partial[b][1] = 0
+//             -- the image loss's rows again: tpgsr_image_loss_finalize(partial, nblk, 1, 0, w, 0, loss) gives loss = w * sum (count 1)
+//   backward: dout = dloss * w * d / sqrt(d^2 + eps)
+// The same access pattern and fixed-order reduction as the L1 pair above.
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float charb(float a, float b, float eps) {
+  const float d = a - b;
+  return sqrtf(__builtin_fmaf(d, d, eps));
+}
+__device__ __forceinline__ float charb_grad(float a, float b, float eps, float g) {
+  const float d = a - b;
+  return g * (d / sqrtf(__builtin_fmaf(d, d, eps)));
+}
+
+__global__ __launch_bounds__(256) void charbonnier_loss_fwd_kernel(const float* __restrict__ out, const float* __restrict__ tgt, long long n4,
+                                                                   long long n, float eps, float* __restrict__ partial) {
+  __shared__ double red[4];
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  double s = 0.0;
+  for (long long i = t0; i < n4; i += stride) {
+    const float4 a = *reinterpret_cast<const float4*>(out + i * 4), b = *reinterpret_cast<const float4*>(tgt + i * 4);
+    s += ((double)charb(a.x, b.x, eps) + (double)charb(a.y, b.y, eps)) + ((double)charb(a.z, b.z, eps) + (double)charb(a.w, b.w, eps));
+  }
+  for (long long i = n4 * 4 + t0; i < n; i += stride) s += (double)charb(out[i], tgt[i], eps);
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 2] = (float)((red[0] + red[1]) + (red[2] + red[3]));
+    partial[blockIdx.x * 2 + 1] = 0.f;
+  }
+}
+
+extern "C" int tpgsr_charbonnier_loss_fwd(const float* out, const float* tgt, long long n, float eps, float* partial, int nblk, void* stream) {
+  TPGSR_CHECK_ARG(out && tgt && partial && nblk > 0 && n > 0 && eps > 0.f, "tpgsr_charbonnier_loss_fwd: bad arguments");
+  const bool vec = ((((uintptr_t)out) | ((uintptr_t)tgt)) & 15) == 0;
+  hipLaunchKernelGGL(charbonnier_loss_fwd_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, out, tgt, vec ? n / 4 : 0, n, eps, partial);
+  TPGSR_LAUNCH_CHECK("tpgsr_charbonnier_loss_fwd");
+}
+
+__global__ __launch_bounds__(256) void charbonnier_loss_bwd_kernel(const float* __restrict__ out, const float* __restrict__ tgt,
+                                                                   const float* __restrict__ dloss, float w, float eps, long long n4, long long n,
+                                                                   float* __restrict__ dout) {
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const float g = dloss[0] * w;
+  for (long long i = t0; i < n4; i += stride) {
+    const float4 a = *reinterpret_cast<const float4*>(out + i * 4), b = *reinterpret_cast<const float4*>(tgt + i * 4);
+    *reinterpret_cast<float4*>(dout + i * 4) =
+        make_float4(charb_grad(a.x, b.x, eps, g), charb_grad(a.y, b.y, eps, g), charb_grad(a.z, b.z, eps, g), charb_grad(a.w, b.w, eps, g));
+  }
+  for (long long i = n4 * 4 + t0; i < n; i += stride) dout[i] = charb_grad(out[i], tgt[i], eps, g);
+}
+
+extern "C" int tpgsr_charbonnier_loss_bwd(const float* out, const float* tgt, const float* dloss, long long n, float eps, float w, float* dout,
+                                          void* stream) {
+  TPGSR_CHECK_ARG(out && tgt && dloss && dout && n > 0 && eps > 0.f, "tpgsr_charbonnier_loss_bwd: bad arguments");
+  const bool vec = ((((uintptr_t)out) | ((uintptr_t)tgt) | ((uintptr_t)dout)) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0, work = n4 > n - 4 * n4 ? n4 : n - 4 * n4;
+  const int grid = (int)max((long long)1, min((long long)4096, (work + 255) / 256));
+  hipLaunchKernelGGL(charbonnier_loss_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, tgt, dloss, w, eps, n4, n, dout);
+  TPGSR_LAUNCH_CHECK("tpgsr_charbonnier_loss_bwd");
+}
+
+// ------------------------------------------------------------------------------------------------------
 // optimiser: global L2 norm, clip coefficient, Adam
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ x, long long n, float* __restrict__ partial) {

@@ -79,6 +79,9 @@ const std::unordered_map<std::string, Entry>& registry() {
       TPGSR_REG(tpgsr_copy_strided), TPGSR_REG(tpgsr_resize_nearest_fwd), TPGSR_REG(tpgsr_resize_nearest_bwd), TPGSR_REG(tpgsr_resize_bilinear_fwd),
       TPGSR_REG(tpgsr_resize_bilinear_bwd), TPGSR_REG(tpgsr_dilate2d), TPGSR_REG(tpgsr_subsample2d), TPGSR_REG(tpgsr_hreduce), TPGSR_REG(tpgsr_hbroadcast),
       TPGSR_REG(tpgsr_bicubic_upsample),
+      TPGSR_REG(tpgsr_tconv4s2_expand), TPGSR_REG(tpgsr_tconv4s2_fold_grad), TPGSR_REG(tpgsr_tconv4s2_small_fwd),
+      TPGSR_REG(tpgsr_tconv4s2_small_bwd_data), TPGSR_REG(tpgsr_tconv4s2_small_bwd_weight), TPGSR_REG(tpgsr_leaky_relu_fwd),
+      TPGSR_REG(tpgsr_leaky_relu_bwd), TPGSR_REG(tpgsr_charbonnier_loss_fwd), TPGSR_REG(tpgsr_charbonnier_loss_bwd),
   };
   return r;
 }

@@ -220,7 +220,8 @@ class FunctionalSREngine(FunctionalEngine):
     arena, weight gradients run on the weight-gradient stream with one batched slab reduce, every multi-consumer tensor of the module's
     forward is a `functional.fork`.  Otherwise operator by operator through autograd: the reference implementation of the recorded mode."""
     role = "sr"
-    scale = 2            # SR grid / LR grid: the operator-level backbones are built for the reference's x2 only (DESIGN section 7)
+    scale = 2            # SR grid / LR grid: the operator-level backbones are built for the reference's x2 only (DESIGN section 7); a module that
+                         # chains x2 stages gives ITS engine instance the module's factor (model/lapsrn.py LapSRN._engine)
     PLAN_NAMES = ("sr_tl_fwd", "sr_tl_bwd")
     OUT, DOUT = "sr", "dsr"
     GRAD_OF = ("prior", "dprior")
@@ -280,8 +281,8 @@ class FunctionalSREngine(FunctionalEngine):
 
 
 class PlainSREngine(FunctionalSREngine):
-    """`FunctionalSREngine` for a backbone WITHOUT a text prior: the reference's prior-free baselines (`--arch srres | rdn | vdsr`,
-    model/{srresnet,rdn,vdsr}.py SRResNet / RDN / VDSR), which the `else:` branch of the train loop (interfaces/super_resolution.py:409-424)
+    """`FunctionalSREngine` for a backbone WITHOUT a text prior: the reference's prior-free baselines (`--arch srres | rdn | vdsr | lapsrn`,
+    model/{srresnet,rdn,vdsr,lapsrn}.py SRResNet / RDN / VDSR / LapSRN), which the `else:` branch of the train loop (interfaces/super_resolution.py:409-424)
     trains with `model(images_lr[:, :channel_num])`.  `SRTrainStep`, `FusedAdam`, `ArenaPool` and `TextSREvaluator` drive the module
     through this adapter; `module(x)` under autograd keeps working on its own.
 
@@ -296,7 +297,7 @@ class PlainSREngine(FunctionalSREngine):
         return dict(lr=torch.empty(*shape, device=self.device))
 
     def forward(self, lr, training, prior=None, slot: int = 0, defer_join: bool = False, pre_done: bool = False) -> torch.Tensor:
-        """lr (N, C, H, W) -> SR image (N, C, 2H, 2W)"""
+        """lr (N, C, H, W) -> SR image (N, C, scale H, scale W)"""
         if prior is not None:
             raise ValueError(f"{type(self.module).__name__} takes no text prior")
         self._check_mode(training)

@@ -237,6 +237,131 @@ def conv_transpose2d(x, w, stride=1, padding=0):
     return _Conv2d.apply(xd, w, None, KH - 1 - ph, KW - 1 - pw, False, True, 1.0)
 
 
+class _TConvK4S2SubPixel(torch.autograd.Function):
+    """ConvTranspose2d(Cin, Cout, 4, 2, 1, bias=False) as the 3x3 pad-1 convolution to 4 Cout channels with the pixel-shuffle store
+    (csrc/tconv4s2.hip): 36 multiply-adds per input pixel and channel pair where the zero-dilated form spends 64, and no dilated tensor.
+    The weight is expanded per call (tpgsr_tconv4s2_expand); the convolution's weight gradient is reduced HERE (not in the plan's batched
+    reduce: the fold reads it next on the same stream) and folded back into the [Cin][Cout][4][4] gradient (tpgsr_tconv4s2_fold_grad)."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        _chk(x, w)
+        x = _c(x)
+        N, H, W, Cx = x.shape
+        Cin, Cout = w.shape[0], w.shape[1]
+        w3 = _new(x, 4 * Cout, Cin, 3, 3)
+        K.tconv4s2_expand(_c(w), Cin, Cout, w3)
+        wt_f, wt_d, *_ = _pack(w3, False, 1.0)
+        g = ConvGeom(N, H, W, Cin, 4 * Cout, 3, 3, 1, 1)
+        out = _new(x, N, 2 * H, 2 * W, Cout)
+        K.conv_fwd(K.make_conv_args(g, x, wt_f, out, out_ps=True))
+        ctx.save_for_backward(x, w, wt_d)
+        ctx.g = g
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, wt_d = ctx.saved_tensors
+        g = ctx.g
+        Cin, Cout = w.shape[0], w.shape[1]
+        dy = _c(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = _new(x, g.N, g.H, g.W, g.Cin)
+            K.conv_fwd(K.make_conv_args(g.dgrad(), dy, wt_d, dx, in_ps=True))
+        if ctx.needs_input_grad[1]:
+            Z = K.wgrad_splits(g.M, g.K, g.Cout, geom=g)
+            part = _new(x, Z, g.K, g.Cout)
+            dw3 = _new(x, 4 * Cout, Cin, 3, 3)
+            sw = _sink(w)
+            with K.side():
+                K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, x), dy, part, None, dy_ps=True, zsplits=Z))
+                K.wgrad_reduce(part, None, Z, g, dw3, None, layout=0, accumulate=False, defer=False)
+                if sw is not None:
+                    K.tconv4s2_fold_grad(dw3, Cin, Cout, sw, accumulate=True)
+                else:
+                    dw = torch.empty_like(w, memory_format=torch.contiguous_format)
+                    K.tconv4s2_fold_grad(dw3, Cin, Cout, dw, accumulate=False)
+        return dx, dw
+
+
+class _TConvK4S2Small(torch.autograd.Function):
+    """the same layer for 1 <= Cin, Cout <= 4 (LapSRN's image branch): three direct kernels, no matrix cores (csrc/tconv4s2.hip)"""
+    NBLK = 512      # rows of the weight gradient's partial sums (at most one per 64 input positions)
+
+    @staticmethod
+    def forward(ctx, x, w):
+        _chk(x, w)
+        x, w = _c(x), _c(w)
+        N, H, W, Cx = x.shape
+        Cin, Cout = w.shape[0], w.shape[1]
+        out = _new(x, N, 2 * H, 2 * W, Cout)
+        K.tconv4s2_small_fwd(x, w, N, H, W, Cin, Cout, out)
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        N, H, W, Cin = x.shape
+        Cout = w.shape[1]
+        dy = _c(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            K.tconv4s2_small_bwd_data(dy, w, N, H, W, Cin, Cout, dx)
+        if ctx.needs_input_grad[1]:
+            nblk = max(1, min(_TConvK4S2Small.NBLK, (N * H * W + 63) // 64))
+            E = Cin * Cout * 16
+            part = _new(x, nblk, E)
+            sw = _sink(w)
+            with K.side():
+                K.tconv4s2_small_bwd_weight(x, dy, N, H, W, Cin, Cout, part, nblk)
+                if sw is not None:
+                    K.reduce_partials(part, nblk, E, sw, accumulate=True)
+                else:
+                    dw = torch.empty_like(w)
+                    K.reduce_partials(part, nblk, E, dw, accumulate=False)
+        return dx, dw
+
+
+# (Cin, Cout) whose 3x3 Cin -> 4 Cout pixel-shuffle-store convolution -- forward, in_ps data gradient, dy_ps weight gradient -- is in the
+# instantiated and tested set of the convolution kernels (the 64 -> 256 convolution of the up-sampling blocks)
+TCONV_SUBPIXEL_PAIRS = frozenset({(64, 64)})
+TCONV_FORMS = ("direct", "subpixel", "dilated")
+
+
+def tconv_k4s2_form(Cin: int, Cout: int) -> str:
+    """the form conv_transpose2d_k4s2 runs a channel pair in"""
+    if Cin <= K.TCONV_SMALL_MAX_C and Cout <= K.TCONV_SMALL_MAX_C:
+        return "direct"
+    return "subpixel" if (Cin, Cout) in TCONV_SUBPIXEL_PAIRS else "dilated"
+
+
+def conv_transpose2d_k4s2(x, w, form: Optional[str] = None):
+    """nn.ConvTranspose2d(Cin, Cout, 4, stride=2, padding=1, bias=False) on an NHWC map, w [Cin][Cout][4][4] -> (N, 2H, 2W, Cout).
+    Up to four channels on both sides: the direct kernels.  64 -> 64: the sub-pixel form (3x3 pixel-shuffle-store convolution on the
+    matrix cores).  Any other pair: the zero-dilated form of conv_transpose2d.  form: a measurement names the form itself
+    (tools/lab/lapsrn_step_time.py); a form the channel pair has no route for raises."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (4, 4):
+        raise ValueError(f"conv_transpose2d_k4s2: a [Cin][Cout][4][4] weight, got {tuple(w.shape)}")
+    Cin, Cout = w.shape[0], w.shape[1]
+    if x.dim() != 4 or x.shape[-1] != Cin:
+        raise ValueError(f"conv_transpose2d_k4s2: input {tuple(x.shape)} is not (N, H, W, {Cin})")
+    auto = tconv_k4s2_form(Cin, Cout)
+    if form is None:
+        form = auto
+    elif form not in TCONV_FORMS:
+        raise ValueError(f"conv_transpose2d_k4s2: form={form!r}, expected one of {TCONV_FORMS}")
+    elif form != "dilated" and form != auto:
+        raise ValueError(f"conv_transpose2d_k4s2: no {form} route for {Cin} -> {Cout} channels")
+    if form == "direct":
+        return _TConvK4S2Small.apply(x, w)
+    if form == "subpixel":
+        return _TConvK4S2SubPixel.apply(x, w)
+    return conv_transpose2d(x, w, 2, 1)
+
+
 def conv2d_strided(x, w, b=None, stride=(1, 1), padding=0):
     """strided conv = stride-1 conv + sub-sampling (only the small conv4_1 of the OPT feature extractor uses it)"""
     return subsample(conv2d(x, w, b, padding), stride[0], stride[1])
@@ -335,6 +460,30 @@ def mish(x):
 
 def tanh(x):
     return _Act.apply(x, "tanh")
+
+
+class _LeakyReLU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, slope):
+        _chk(x)
+        x = _c(x)
+        out = torch.empty_like(x)
+        K.leaky_relu_fwd(x, x.numel(), slope, out)
+        ctx.save_for_backward(x)
+        ctx.slope = slope
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        K.leaky_relu_bwd(x, _c(dy), x.numel(), ctx.slope, dx)
+        return dx, None
+
+
+def leaky_relu(x, slope: float = 0.01):
+    """nn.LeakyReLU(slope): any element count; the derivative at x <= 0 is `slope` (ATen's)"""
+    return _LeakyReLU.apply(x, float(slope))
 
 
 class _PReLU(torch.autograd.Function):

@@ -36,15 +36,18 @@ def _warn_hw_queues(collective: bool):
                       "(INTEGRATION.md section 4)." % os.environ.get("GPU_MAX_HW_QUEUES", "unset (HIP default 4)"), RuntimeWarning, stacklevel=3)
 
 
-IMAGE_CRITS = ("image_loss", "mse", "l1")
+IMAGE_CRITS = ("image_loss", "mse", "l1", "l1_charbonnier")
+CHARBONNIER_EPS = 1e-6      # L1_Charbonnier_loss.eps (model/lapsrn.py:131)
 
 
 def _image_crit(who: str, image_crit: str, gradient, loss_weight):
     """the image criterion of a train step (interfaces/base.py:332-368) -> (gradient, w0, w1) of its kernels: "image_loss" =
     ImageLoss(gradient, loss_weight) of tsrn / tsrn_tl_cascade; "mse" = nn.MSELoss() of srres / vdsr / srresnet_tl / srcnn_tl / vdsr_tl (the
-    image-loss kernels with the gradient term off and w0 = 1); "l1" = nn.L1Loss() of rdn / rdn_tl (tpgsr_l1_loss_fwd / _bwd)"""
+    image-loss kernels with the gradient term off and w0 = 1); "l1" = nn.L1Loss() of rdn / rdn_tl (tpgsr_l1_loss_fwd / _bwd);
+    "l1_charbonnier" = lapsrn.L1_Charbonnier_loss() of lapsrn (interfaces/base.py:351-353; tpgsr_charbonnier_loss_fwd / _bwd): a SUM over
+    the elements, so `.mean()` of the scalar changes nothing and the step's loss is 100 times that sum"""
     if image_crit not in IMAGE_CRITS:
-        raise ValueError(f"{who}: image_crit={image_crit!r}, expected 'image_loss', 'mse' or 'l1'")
+        raise ValueError(f"{who}: image_crit={image_crit!r}, expected 'image_loss', 'mse', 'l1' or 'l1_charbonnier'")
     if image_crit != "image_loss":
         return False, 1.0, 0.0
     return bool(gradient), float(loss_weight[0]), float(loss_weight[1])
@@ -52,6 +55,10 @@ def _image_crit(who: str, image_crit: str, gradient, loss_weight):
 
 def _image_crit_value(image_crit, sr, hr, N, C, H2, W2, gradient, w0, w1, part, loss):
     """criterion(sr, hr).mean() * 100 -> the device scalar `loss` (two launches on the current stream)"""
+    if image_crit == "l1_charbonnier":      # a sum, not a mean: the finalize divides by 1
+        K.charbonnier_loss_fwd(sr, hr, sr.numel(), CHARBONNIER_EPS, part, _NBLK_IMG)
+        K.image_loss_finalize(part, _NBLK_IMG, 1, 0, w0 * 100.0, 0.0, loss)
+        return
     if image_crit == "l1":
         K.l1_loss_fwd(sr, hr, sr.numel(), part, _NBLK_IMG)
     else:
@@ -62,7 +69,9 @@ def _image_crit_value(image_crit, sr, hr, N, C, H2, W2, gradient, w0, w1, part, 
 
 def _image_crit_grad(image_crit, sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, dsr):
     """d (criterion(sr, hr).mean() * dloss) / d sr -> dsr"""
-    if image_crit == "l1":
+    if image_crit == "l1_charbonnier":
+        K.charbonnier_loss_bwd(sr, hr, dloss, sr.numel(), CHARBONNIER_EPS, w0, dsr)
+    elif image_crit == "l1":
         K.l1_loss_bwd(sr, hr, dloss, sr.numel(), w0, dsr)
     else:
         K.image_loss_bwd(sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, dsr)
@@ -70,7 +79,7 @@ def _image_crit_grad(image_crit, sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, 
 
 def _sr_scale(who, modules) -> int:
     """SR grid / LR grid of a step's SR network(s) (`scale` of their engines: 2 ** up-sampling stages for TSRN / TSRN_TL, 2 for the
-    operator-level backbones); every stage of a cascade compares with the same HR batch, so they must agree"""
+    operator-level backbones but LapSRN, whose engine carries the module's factor); every stage of a cascade compares with the same HR batch, so they must agree"""
     scales = sorted({int(m._engine().scale) for m in modules})
     if len(scales) != 1:
         raise ValueError(f"{who}: the SR networks of one cascade disagree on scale_factor ({scales})")
@@ -98,6 +107,7 @@ class TSRNTrainStep:
         SRTrainStep(srresnet.SRResNet(mask=True), image_crit="mse")          # train_SRResNet.sh
         SRTrainStep(rdn.RDN(), image_crit="l1", channels=3)                  # train_RDN.sh
         SRTrainStep(vdsr.VDSR(), image_crit="mse", channels=3)
+        SRTrainStep(lapsrn.LapSRN(scale_factor=4), image_crit="l1_charbonnier", channels=3)      # --arch lapsrn, no --mask
     image_crit: the criterion interfaces/base.py:332-347 pairs with the architecture (`_image_crit` above).  channels: the reference's
     channel_num -- the step feeds lr[:, :channels] and compares with hr[:, :channels] (:410-416); the prefix is gathered by a kernel
     launch (tpgsr_copy_strided), so capture() / replay() work on it."""
@@ -696,7 +706,7 @@ class TextSREvaluator:
                  channels: Optional[int] = None):
         self.sr = list(sr_models) if isinstance(sr_models, (list, tuple)) else [sr_models]
         # tpg_models=None: the prior-free pass (interfaces/super_resolution.py:770-793) -- sr = sr_models[0](lr[:, :channels]) for a module
-        # with an engine (tsrn.TSRN, srresnet.SRResNet, rdn.RDN, vdsr.VDSR) or a model.bicubic.BICUBIC; no text-prior generator runs
+        # with an engine (tsrn.TSRN, srresnet.SRResNet, rdn.RDN, vdsr.VDSR, lapsrn.LapSRN) or a model.bicubic.BICUBIC; no text-prior generator runs
         self.plain = tpg_models is None
         self.channels = None if channels is None else int(channels)
         if self.plain:
@@ -785,6 +795,10 @@ class TextSREvaluator:
         srs, priors = self.super_resolve(images_lr)
         sr = srs[-1]
         hr_m = images_hr
+        if self.plain and tuple(sr.shape[2:]) != tuple(images_hr.shape[2:]):
+            s = sr.shape[2] // images_lr.shape[2]       # (the engine's factor: what the network made of the LR grid)
+            raise ValueError(f"TextSREvaluator: hr is {tuple(images_hr.shape)}, expected a {tuple(sr.shape[2:])} grid for the "
+                             f"{tuple(images_lr.shape)} low-resolution batch of a x{s} network")
         if sr.shape[1] != images_hr.shape[1]:
             # prior-free pass on a channel prefix: PSNR / SSIM read the first three planes of both images (utils/ssim_psnr.py:12), so HR is
             # cut to the SR image's plane count

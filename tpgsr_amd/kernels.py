@@ -836,12 +836,13 @@ def deferring() -> bool:
     return _REC is not None and _REC.deferred is not None
 
 
-def wgrad_reduce(part, dbpart, Z, g: ConvGeom, dw, db=None, *, layout=0, accumulate=True, gscale=1.0, real=None):
+def wgrad_reduce(part, dbpart, Z, g: ConvGeom, dw, db=None, *, layout=0, accumulate=True, gscale=1.0, real=None, defer=True):
     """real = (Cin, KH, KW, cin_ld) of the parameter when the GEMM ran on a zero-padded operand (slab rows k = tap*cin_ld + ci
-    with ci >= Cin or tap >= KH*KW are skipped); default: the geometry's own"""
+    with ci >= Cin or tap >= KH*KW are skipped); default: the geometry's own.  defer=False: launched here even in a plan that batches
+    its reduces -- for a caller whose next launch on this stream reads dw (conv_transpose2d_k4s2's fold)"""
     Cin, KH, KW, cin_ld = real if real is not None else (g.Cin, g.KH, g.KW, 0)
     item = (part, dbpart, Z, g.K, Cin, g.Cout, KH, KW, layout, dw, db, int(accumulate), float(gscale), cin_ld)
-    if deferring():   # the caller gave this layer its own slab buffers; reduced by flush_wgrad_reduces()
+    if deferring() and defer:   # the caller gave this layer its own slab buffers; reduced by flush_wgrad_reduces()
         _REC.deferred.append(item + (_REC.sid == 2,))       # (tagged: produced on the leaf stream)
     elif real is not None:
         _reduce_program([item])
@@ -964,6 +965,14 @@ def prelu_fwd(x, alpha, n, y):
 
 def prelu_bwd(x, alpha, dy, dy2, n, dx, dalpha_partial, nblk):
     _launch("tpgsr_prelu_bwd", _p(x), _p(alpha), _p(dy), _p(dy2), n, _p(dx), _p(dalpha_partial), nblk)
+
+
+def leaky_relu_fwd(x, n, slope, y):
+    _launch("tpgsr_leaky_relu_fwd", _p(x), n, slope, _p(y))
+
+
+def leaky_relu_bwd(x, dy, n, slope, dx):
+    _launch("tpgsr_leaky_relu_bwd", _p(x), _p(dy), n, slope, _p(dx))
 
 
 def add(a, b, n, out):
@@ -1288,6 +1297,23 @@ def l1_loss_bwd(out, tgt, dloss, n, w, dout):
     _launch("tpgsr_l1_loss_bwd", _p(out), _p(tgt), _p(dloss), n, w, _p(dout))
 
 
+def charbonnier_loss_fwd(out, tgt, n, eps, partial, nblk):
+    """partial [nblk][2] = {sum sqrt((out - tgt)^2 + eps) per workgroup, 0}: image_loss_finalize(partial, nblk, 1, 0, w, 0.0, loss) makes
+    w * SUM of it (the reference's criterion is a sum: the count is 1)"""
+    if out.numel() != n or tgt.numel() != n:
+        raise ValueError(f"charbonnier_loss_fwd: out / tgt have {out.numel()} / {tgt.numel()} elements, expected {n}")
+    if partial.numel() < 2 * nblk:
+        raise ValueError(f"charbonnier_loss_fwd: partial holds {partial.numel()} floats, {nblk} workgroups write {2 * nblk}")
+    _launch("tpgsr_charbonnier_loss_fwd", _p(out), _p(tgt), n, eps, _p(partial), nblk)
+
+
+def charbonnier_loss_bwd(out, tgt, dloss, n, eps, w, dout):
+    """dout = dloss[0] * w * d / sqrt(d^2 + eps), d = out - tgt"""
+    if out.numel() != n or tgt.numel() != n or dout.numel() != n:
+        raise ValueError(f"charbonnier_loss_bwd: out / tgt / dout have {out.numel()} / {tgt.numel()} / {dout.numel()} elements, expected {n}")
+    _launch("tpgsr_charbonnier_loss_bwd", _p(out), _p(tgt), _p(dloss), n, eps, w, _p(dout))
+
+
 def sumsq_partial(x, n, partial, nblk):
     _launch("tpgsr_sumsq_partial", _p(x), n, _p(partial), nblk)
 
@@ -1382,6 +1408,52 @@ def dilate2d(inp, N, H, W, C_, sh, sw, out):
 
 def subsample2d(inp, N, H, W, C_, sh, sw, out):
     _launch("tpgsr_subsample2d", _p(inp), N, H, W, C_, sh, sw, _p(out))
+
+
+# ---- ConvTranspose2d(k 4, stride 2, padding 1) (csrc/tconv4s2.hip) ---------------------------------------------------
+TCONV_SMALL_MAX_C = 4      # channel counts the direct kernels take (the image branch of LapSRN)
+
+
+def tconv4s2_expand(w, Cin, Cout, w3):
+    """w [Cin][Cout][4][4] -> w3 [4 Cout][Cin][3][3]: the 3x3 pixel-shuffle convolution the layer equals"""
+    if w.numel() != Cin * Cout * 16 or w3.numel() != Cin * Cout * 36:
+        raise ValueError(f"tconv4s2_expand: w / w3 have {w.numel()} / {w3.numel()} elements, expected {Cin * Cout * 16} / {Cin * Cout * 36}")
+    _launch("tpgsr_tconv4s2_expand", _p(w), Cin, Cout, _p(w3))
+
+
+def tconv4s2_fold_grad(dw3, Cin, Cout, dw, accumulate=True):
+    """dW3 [4 Cout][Cin][3][3] -> dw [Cin][Cout][4][4] (+= when accumulate)"""
+    if dw.numel() != Cin * Cout * 16 or dw3.numel() != Cin * Cout * 36:
+        raise ValueError(f"tconv4s2_fold_grad: dw / dw3 have {dw.numel()} / {dw3.numel()} elements, expected {Cin * Cout * 16} / {Cin * Cout * 36}")
+    _launch("tpgsr_tconv4s2_fold_grad", _p(dw3), Cin, Cout, _p(dw), int(accumulate))
+
+
+def _tconv_small_check(who, N, H, W, Cin, Cout, x, y, w=None):
+    """the refusals of the C launch functions, made before anything is launched (or recorded)"""
+    if not (1 <= Cin <= TCONV_SMALL_MAX_C and 1 <= Cout <= TCONV_SMALL_MAX_C):
+        raise ValueError(f"{who}: the direct kernels take 1 to {TCONV_SMALL_MAX_C} input and output channels, got {Cin} -> {Cout}")
+    if min(N, H, W) < 1 or N * H * W >= 1 << 27:
+        raise ValueError(f"{who}: needs 1 <= N H W < 2^27 input positions (32-bit indices), got {N} x {H} x {W}")
+    if x.numel() != N * H * W * Cin or y.numel() != N * 4 * H * W * Cout or (w is not None and w.numel() != Cin * Cout * 16):
+        raise ValueError(f"{who}: tensor sizes do not match N {N}, H {H}, W {W}, Cin {Cin}, Cout {Cout}")
+
+
+def tconv4s2_small_fwd(x, w, N, H, W, Cin, Cout, y):
+    _tconv_small_check("tconv4s2_small_fwd", N, H, W, Cin, Cout, x, y, w)
+    _launch("tpgsr_tconv4s2_small_fwd", _p(x), _p(w), N, H, W, Cin, Cout, _p(y))
+
+
+def tconv4s2_small_bwd_data(dy, w, N, H, W, Cin, Cout, dx):
+    _tconv_small_check("tconv4s2_small_bwd_data", N, H, W, Cin, Cout, dx, dy, w)
+    _launch("tpgsr_tconv4s2_small_bwd_data", _p(dy), _p(w), N, H, W, Cin, Cout, _p(dx))
+
+
+def tconv4s2_small_bwd_weight(x, dy, N, H, W, Cin, Cout, partial, nblk):
+    """partial [nblk][Cin Cout 16]: reduce_partials(partial, nblk, Cin * Cout * 16, dw, accumulate) finishes it"""
+    _tconv_small_check("tconv4s2_small_bwd_weight", N, H, W, Cin, Cout, x, dy)
+    if not 1 <= nblk <= 65536 or partial.numel() < nblk * Cin * Cout * 16:
+        raise ValueError(f"tconv4s2_small_bwd_weight: partial holds {partial.numel()} floats, {nblk} workgroups write {nblk * Cin * Cout * 16}")
+    _launch("tpgsr_tconv4s2_small_bwd_weight", _p(x), _p(dy), N, H, W, Cin, Cout, _p(partial), nblk)
 
 
 def hreduce(inp, N, H, W, C_, scale, out):
