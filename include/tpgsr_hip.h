@@ -436,6 +436,22 @@ int tpgsr_prelu_bwd(const float* x, const float* alpha, const float* dy, const f
 /* nn.LeakyReLU(slope), any n: y = x > 0 ? x : x * slope; dx = x > 0 ? dy : dy * slope (derivative `slope` at x <= 0, as ATen's) */
 int tpgsr_leaky_relu_fwd(const float* x, long long n, float slope, float* y, void* stream);
 int tpgsr_leaky_relu_bwd(const float* x, const float* dy, long long n, float slope, float* dx, void* stream);
+/* Glue of the in-place residual dense block (csrc/dense.hip; functional.dense_block).  Buffers are NHWC rows [M][ld], a window is the
+ * channels [coff, coff + C) of every row; nothing outside the windows and no row at or behind M is touched.  16-byte accesses when every
+ * pointer, row length and window bound is a multiple of 16 bytes, element by element otherwise.
+ * tpgsr_leaky_relu_window: LeakyReLU(slope) in place on a window.
+ * tpgsr_scaled_add: out = alpha * a + b over windows, a rounded fp32 product then a rounded fp32 sum (no fused multiply-add); b == NULL:
+ *   out = alpha * a.  out may alias a or b window for window.
+ * tpgsr_dense_bwd_step: one pass of the block's in-place backward over the gradient buffer G [M][ld].  dx == NULL:
+ *   G[:, 0:c_acc] += T (T dense [M][c_acc]; T == NULL: nothing to add, only the mask window is visited), then
+ *   G[:, mask_coff : mask_coff + mask_c] *= (Dbuf[same window] > 0 ? 1 : slope) -- Dbuf [M][ld] holds POST-activation values (their sign is
+ *   the pre-activation's for slope > 0; derivative `slope` at +-0, as ATen's); mask_c == 0 allowed with T; the window lies inside [0, c_acc).
+ *   dx != NULL (the last pass; needs T, mask_c == 0): dx[:, 0:c_acc] = (G + T) + skip, dx / skip dense [M][c_acc], skip optional, G unchanged. */
+int tpgsr_leaky_relu_window(float* buf, int ld, int coff, int C, long long M, float slope, void* stream);
+int tpgsr_scaled_add(const float* a, int a_ld, int a_coff, const float* b, int b_ld, int b_coff, float alpha, float* out, int out_ld,
+                     int out_coff, long long M, int C, void* stream);
+int tpgsr_dense_bwd_step(float* G, int ld, const float* T, int c_acc, const float* Dbuf, int mask_coff, int mask_c, float slope,
+                         const float* skip, float* dx, long long M, void* stream);
 /* out = a + b (b optional scale) ; out = a*mish'(x) etc. */
 int tpgsr_add(const float* a, const float* b, long long n, float* out, void* stream);
 /* out = ((a0 + a1) + a2) + ... + a[k-1], 2 <= k <= 8 addends of n floats (a[k..7] ignored): one launch, fixed left-to-right fp32 order

@@ -535,6 +535,35 @@ def add(a, b):
     return _Add.apply(a, b)
 
 
+class _ScaledAdd(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, alpha):
+        _chk(a, b)
+        if a.shape != b.shape:
+            raise ValueError(f"scaled_add: {tuple(a.shape)} vs {tuple(b.shape)}")
+        a, b = _c(a), _c(b)
+        C = a.shape[-1]
+        out = torch.empty_like(a)
+        K.scaled_add(a, C, 0, b, C, 0, alpha, out, C, 0, a.numel() // C, C)
+        ctx.alpha = alpha
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        da = None
+        if ctx.needs_input_grad[0]:
+            g = _c(g)
+            C = g.shape[-1]
+            da = torch.empty_like(g)
+            K.scaled_add(g, C, 0, None, 0, 0, ctx.alpha, da, C, 0, g.numel() // C, C)
+        return da, (g if ctx.needs_input_grad[1] else None), None      # (the second term is passed through: no launch)
+
+
+def scaled_add(a, b, alpha: float):
+    """alpha * a + b (the 0.2-scaled residuals of ESRGAN's blocks, model/esrgan.py:36, :52): one launch forward, one (alpha * g) backward"""
+    return _ScaledAdd.apply(a, b, float(alpha))
+
+
 class _Fork(torch.autograd.Function):
     """x -> n views of x for a tensor with n consumers (the identity branch of a residual block, a text-prior map fed to every block):
     the incoming gradients are summed here by ONE launch (tpgsr_add for two, tpgsr_add_n for up to eight, left to right in consumer
@@ -602,6 +631,147 @@ class _Cat(torch.autograd.Function):
 
 def cat(xs: Sequence[torch.Tensor]):
     return _Cat.apply(*xs)
+
+
+# ---- residual dense block (ESRGAN's ResidualDenseBlock_5C, model/esrgan.py:16-36) -------------------------------------------------
+class _DenseBlock(torch.autograd.Function):
+    """y = res_scale * conv5([x, x1, x2, x3, x4]) + x with x_k = LeakyReLU(conv_k([x, x1 .. x_{k-1}])), on ONE concatenation buffer
+    D [M][nf + 4 gc]: convolution k reads the channel prefix [0, Cin_k) of D and writes the window behind it (input and output share the
+    buffer, the windows are disjoint), tpgsr_leaky_relu_window activates the window in place.  No concatenation is ever copied: one
+    tpgsr_copy_strided puts x into the buffer.
+
+    The backward pass works in place the same way on a gradient buffer G [M][nf + 4 gc]: conv5's data gradient fills it, then for k = 4 .. 1
+    tpgsr_dense_bwd_step masks window k by the activation's derivative (read from D's POST-activation values: same sign for slope > 0; the
+    first call is mask-only, T = NULL), conv k's data gradient goes into a dense T_k [M][Cin_k], and the next step adds T_k to G's prefix
+    while it masks window k - 1.  The last step writes dx = (G[:, :nf] + T_1) + dy.  res_scale is applied to dy by one tpgsr_scaled_add
+    launch (it is NOT folded into conv5's packed weight).  Window k of G is final once masked -- later steps only touch the columns in
+    front of it -- so the weight-gradient launches on the side stream read it unordered with the caller's stream moving on; G and every T
+    are the operator's own allocations (a recorded plan keeps them alive)."""
+
+    @staticmethod
+    def forward(ctx, x, slope, res_scale, *wb):
+        ws, bs = wb[:5], wb[5:]
+        _chk(x, *ws, *bs)
+        x = _c(x)
+        N, H, W, nf = x.shape
+        gc = ws[0].shape[0]
+        Ct = nf + 4 * gc
+        M = N * H * W
+        D = _new(x, N, H, W, Ct)
+        K.copy_strided(x, nf, 0, D, Ct, 0, M, nf)
+        geoms, wds = [], []
+        for k in range(4):
+            Cin = nf + k * gc
+            wt_f, wt_d, *_ = _pack(ws[k], False, 1.0)
+            g = ConvGeom(N, H, W, Cin, gc, 3, 3, 1, 1)
+            K.conv_fwd(K.make_conv_args(g, D, wt_f, D, bias=bs[k], in_ld=Ct, out_ld=Ct, out_coff=Cin))
+            K.leaky_relu_window(D, Ct, Cin, gc, M, slope)
+            geoms.append(g)
+            wds.append(wt_d)
+        wt_f, wt_d, *_ = _pack(ws[4], False, 1.0)
+        g = ConvGeom(N, H, W, Ct, nf, 3, 3, 1, 1)
+        y = _new(x, N, H, W, nf)
+        K.conv_fwd(K.make_conv_args(g, D, wt_f, y, bias=bs[4]))
+        K.scaled_add(y, nf, 0, D, Ct, 0, res_scale, y, nf, 0, M, nf)      # in place on x5: the backward needs D only
+        geoms.append(g)
+        wds.append(wt_d)
+        ctx.save_for_backward(D, *ws, *wds)
+        ctx.cfg = (geoms, slope, res_scale, nf, gc)
+        ctx.bias_ptrs = [None if b is None else b.data_ptr() for b in bs]
+        return y
+
+    @staticmethod
+    def _wgrad(ctx, k, g, w, D, Ct, dy, dy_ld, dy_coff):
+        """weight / bias gradient of convolution k exactly as _Conv2d.backward: slabs on the side stream, reduced into the sink or a tensor"""
+        has_b = ctx.bias_ptrs[k] is not None
+        if not (ctx.needs_input_grad[3 + k] or (has_b and ctx.needs_input_grad[8 + k])):
+            return None, None
+        dw = db = None
+        Z = K.wgrad_splits(g.M, g.K, g.Cout, geom=g)
+        part = _new(D, Z, g.K, g.Cout)
+        dbp = _new(D, Z, g.Cout) if has_b else None
+        sw = _sink(w)
+        with K.side():
+            K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, D, in_ld=Ct), dy, part, dbp, dy_ld=dy_ld, dy_coff=dy_coff, zsplits=Z))
+            if sw is not None:
+                sb = GRAD_SINK.get(ctx.bias_ptrs[k]) if has_b else None
+                assert not has_b or sb is not None, "a sunk weight gradient needs its bias gradient sunk too"
+                K.wgrad_reduce(part, dbp, Z, g, sw, sb, layout=0, accumulate=True)
+            else:
+                dw = torch.empty_like(w)
+                db = _new(D, g.Cout) if has_b else None
+                K.wgrad_reduce(part, dbp, Z, g, dw, db, layout=0, accumulate=False)
+        return dw, db
+
+    @staticmethod
+    def backward(ctx, dy):
+        D, *rest = ctx.saved_tensors
+        ws, wds = rest[:5], rest[5:]
+        geoms, slope, res_scale, nf, gc = ctx.cfg
+        dy = _c(dy)
+        N, H, W, Ct = D.shape
+        M = N * H * W
+        dws, dbs = [None] * 5, [None] * 5
+        dx5 = torch.empty_like(dy)
+        K.scaled_add(dy, nf, 0, None, 0, 0, res_scale, dx5, nf, 0, M, nf)
+        G = _new(D, N, H, W, Ct)
+        K.conv_fwd(K.make_conv_args(geoms[4].dgrad(), dx5, wds[4], G))
+        dws[4], dbs[4] = _DenseBlock._wgrad(ctx, 4, geoms[4], ws[4], D, Ct, dx5, None, 0)
+        T = None
+        for k in (3, 2, 1, 0):
+            g = geoms[k]
+            Cin = g.Cin
+            K.dense_bwd_step(G, Ct, T, Cin + gc, D, Cin, gc, slope, M)      # (k = 3: mask only, every column of G is conv5's alone so far)
+            dws[k], dbs[k] = _DenseBlock._wgrad(ctx, k, g, ws[k], D, Ct, G, Ct, Cin)
+            T = _new(D, N, H, W, Cin)
+            K.conv_fwd(K.make_conv_args(g.dgrad(), G, wds[k], T, in_ld=Ct, in_coff=Cin))
+        dx = torch.empty_like(dy)
+        K.dense_bwd_step(G, Ct, T, nf, None, 0, 0, slope, M, skip=dy, dx=dx)
+        return (dx, None, None, *dws, *dbs)
+
+
+DENSE_FORMS = ("inplace", "composed")
+
+
+def _dense_block_composed(x, ws, bs, slope, res_scale):
+    """the block as model/rdn.py composes its dense layers: fork / cat / conv2d / leaky_relu, the scaled residual by scaled_add"""
+    cur, skip = fork(x)
+    for k in range(4):
+        cur, keep = fork(cur)
+        cur = cat([keep, leaky_relu(conv2d(cur, ws[k], bs[k], 1), slope)])
+    return scaled_add(conv2d(cur, ws[4], bs[4], 1), skip, res_scale)
+
+
+def dense_block(x, weights, biases=None, slope: float = 0.2, res_scale: float = 0.2, form: Optional[str] = None):
+    """ResidualDenseBlock_5C (reference model/esrgan.py:16-36) on an NHWC map x (N, H, W, nf): weights = five 3x3 convolution weights
+    [gc | nf][nf + k gc][3][3], biases = five vectors, or None entries / None.  form "inplace": the block on one concatenation buffer
+    (_DenseBlock; channel counts that are multiples of 4); "composed": the same mathematics over fork / cat / conv2d / leaky_relu;
+    None: in place where the channel counts allow it, composed otherwise."""
+    if form is not None and form not in DENSE_FORMS:
+        raise ValueError(f"dense_block: form={form!r}, expected one of {DENSE_FORMS} or None")
+    ws = list(weights)
+    bs = [None] * 5 if biases is None else list(biases)
+    if len(ws) != 5 or len(bs) != 5:
+        raise ValueError("dense_block: five convolution weights (and five biases or None)")
+    if x.dim() != 4:
+        raise ValueError(f"dense_block: input {tuple(x.shape)} is not (N, H, W, nf)")
+    nf, gc = x.shape[-1], ws[0].shape[0]
+    for k, w in enumerate(ws):
+        want = (nf if k == 4 else gc, nf + k * gc, 3, 3)
+        if tuple(w.shape) != want:
+            raise ValueError(f"dense_block: weight {k + 1} is {tuple(w.shape)}, expected {want}")
+    fits = nf % 4 == 0 and gc % 4 == 0
+    if form is None:
+        form = DENSE_DEFAULT_FORM if fits else "composed"
+    elif form == "inplace" and not fits:
+        raise ValueError(f"dense_block: the in-place form takes channel counts that are multiples of 4, got nf {nf}, gc {gc}")
+    if form == "composed":
+        return _dense_block_composed(x, ws, bs, float(slope), float(res_scale))
+    return _DenseBlock.apply(x, float(slope), float(res_scale), *ws, *bs)
+
+
+# the form `form=None` runs where both fit: decided by tools/lab/rrdb_step_time.py (profiles/rrdb_step_time.md)
+DENSE_DEFAULT_FORM = "inplace"
 
 
 # ---- pooling / resampling -------------------------------------------------------------------------------------------------

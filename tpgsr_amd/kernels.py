@@ -975,6 +975,21 @@ def leaky_relu_bwd(x, dy, n, slope, dx):
     _launch("tpgsr_leaky_relu_bwd", _p(x), _p(dy), n, slope, _p(dx))
 
 
+def leaky_relu_window(buf, ld, coff, C_, M, slope):
+    """LeakyReLU in place on the channels [coff, coff + C_) of the rows [M][ld] (csrc/dense.hip)"""
+    _launch("tpgsr_leaky_relu_window", _p(buf), ld, coff, C_, M, slope)
+
+
+def scaled_add(a, a_ld, a_coff, b, b_ld, b_coff, alpha, out, out_ld, out_coff, M, C_):
+    """out = alpha * a + b over channel windows (b None: out = alpha * a); out may alias a or b window for window"""
+    _launch("tpgsr_scaled_add", _p(a), a_ld, a_coff, _p(b), b_ld, b_coff, alpha, _p(out), out_ld, out_coff, M, C_)
+
+
+def dense_bwd_step(G, ld, T, c_acc, Dbuf, mask_coff, mask_c, slope, M, skip=None, dx=None):
+    """one pass of functional.dense_block's in-place backward (tpgsr_dense_bwd_step in include/tpgsr_hip.h)"""
+    _launch("tpgsr_dense_bwd_step", _p(G), ld, _p(T), c_acc, _p(Dbuf), mask_coff, mask_c, slope, _p(skip), _p(dx), M)
+
+
 def add(a, b, n, out):
     _launch("tpgsr_add", _p(a), _p(b), n, _p(out))
 
