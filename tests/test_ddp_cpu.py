@@ -4,6 +4,7 @@ per-micro-batch BatchNorm statistics, and identical parameters on every rank aft
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
@@ -14,6 +15,16 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 def _flat(grads):
     return torch.cat([g.reshape(-1) for g in grads])
+
+
+def _put(q, rank, *vals):
+    """results travel BY VALUE (numpy), not as tensors: a tensor in a multiprocessing queue is a handle to shared memory that the receiver
+    opens by connecting back to the sender -- an EOFError in the parent when the worker has exited before the parent reads the queue"""
+    q.put((rank,) + tuple(v.numpy() if torch.is_tensor(v) else v for v in vals))
+
+
+def _get(q):
+    return tuple(torch.from_numpy(v) if isinstance(v, np.ndarray) else v for v in q.get(timeout=240))
 
 
 def _worker(rank, world, port, q):
@@ -51,7 +62,7 @@ def _worker(rank, world, port, q):
         ofs += n
     O.clip_grad_norm_(gl, 0.25)
     opt.step(gl)
-    q.put((rank, _flat([p[k].detach() for k in keys]), g))
+    _put(q, rank, _flat([p[k].detach() for k in keys]), g)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -66,7 +77,7 @@ def test_two_rank_exchange_matches_gradient_accumulation():
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for pr in procs:
         pr.start()
-    res = sorted([q.get(timeout=240) for _ in range(2)], key=lambda t: t[0])
+    res = sorted([_get(q) for _ in range(2)], key=lambda t: t[0])
     for pr in procs:
         pr.join(60)
     (_, p0, g0), (_, p1, g1) = res
@@ -108,7 +119,7 @@ def _bucket_worker(rank, world, port, q):
     ex.finish()                        # launches bucket 1, waits for both, averages
     ex.launch(0)                       # next step: buckets can be launched again
     ex.finish()
-    q.put((rank, mine, flat.clone(), twice))
+    _put(q, rank, mine, flat.clone(), twice)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -123,7 +134,7 @@ def test_bucketed_overlapped_exchange_two_ranks():
     procs = [ctx.Process(target=_bucket_worker, args=(r, 2, port, q)) for r in range(2)]
     for pr in procs:
         pr.start()
-    res = sorted([q.get(timeout=240) for _ in range(2)], key=lambda t: t[0])
+    res = sorted([_get(q) for _ in range(2)], key=lambda t: t[0])
     for pr in procs:
         pr.join(60)
     (_, a0, f0, tw0), (_, a1, f1, tw1) = res
@@ -154,7 +165,7 @@ def _three_bucket_worker(rank, world, port, q):
     ex.launch(1)
     flat[300:340] += 2.0               # ... and only the first layers after the early bucket left
     ex.finish()
-    q.put((rank, mine, flat.clone()))
+    _put(q, rank, mine, flat.clone())
     dist.barrier()
     dist.destroy_process_group()
 
@@ -168,7 +179,7 @@ def test_three_buckets_launched_out_of_address_order_two_ranks():
     procs = [ctx.Process(target=_three_bucket_worker, args=(r, 2, port, q)) for r in range(2)]
     for pr in procs:
         pr.start()
-    res = sorted([q.get(timeout=240) for _ in range(2)], key=lambda t: t[0])
+    res = sorted([_get(q) for _ in range(2)], key=lambda t: t[0])
     for pr in procs:
         pr.join(60)
     (_, a0, f0), (_, a1, f1) = res
@@ -206,7 +217,7 @@ def _seven_bucket_worker(rank, world, port, q):
                 flat[lo:hi] += float(step + 1)
                 written[lo:hi] += float(step + 1)
     ex.finish()
-    q.put((rank, mine, flat.clone(), written))
+    _put(q, rank, mine, flat.clone(), written)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -221,7 +232,7 @@ def test_seven_buckets_of_the_three_student_step_two_ranks():
     procs = [ctx.Process(target=_seven_bucket_worker, args=(r, 2, port, q)) for r in range(2)]
     for pr in procs:
         pr.start()
-    res = sorted([q.get(timeout=240) for _ in range(2)], key=lambda t: t[0])
+    res = sorted([_get(q) for _ in range(2)], key=lambda t: t[0])
     for pr in procs:
         pr.join(60)
     (_, a0, f0, w0), (_, a1, f1, w1) = res
@@ -296,7 +307,7 @@ def _dp_worker(rank, world, port, q):
     dpf = DataParallel(fused)
     assert fused._grad_sync == dpf._sync
     fused._grad_sync(eng)
-    q.put((rank, p0, g, eng.arena.flat.clone(), eng.arena.grad.clone()))
+    _put(q, rank, p0, g, eng.arena.flat.clone(), eng.arena.grad.clone())
     dist.barrier()
     dist.destroy_process_group()
 
@@ -311,7 +322,7 @@ def test_dataparallel_wrapper_two_ranks_hooked_and_fused_paths():
     procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
     for pr in procs:
         pr.start()
-    res = sorted([q.get(timeout=240) for _ in range(2)], key=lambda t: t[0])
+    res = sorted([_get(q) for _ in range(2)], key=lambda t: t[0])
     for pr in procs:
         pr.join(60)
     (_, pa, ga, fa, gfa), (_, pb, gb, fb, gfb) = res

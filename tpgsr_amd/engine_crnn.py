@@ -5,7 +5,10 @@ Same machinery as the TSRN engine: NHWC workspaces, BN/ReLU folded into consumer
 all GEMM-shaped work (convs, LSTM input projections, the per-step recurrent projections, embeddings, every weight
 gradient) on the fp32-MFMA implicit-GEMM kernel, gate math in small fused kernels, parameter gradients written into
 the flat arena.  The sequence tensor is kept batch-major [N][T][C] (== NHWC with H = 1, W = T), so a time step of the
-recurrence is a 1x1 "conv" that reads pixel t of every image (negative pad_w selects the column)."""
+recurrence is a 1x1 "conv" that reads pixel t of every image (negative pad_w selects the column).
+
+The engine's schedule switches (TPGSR_CRNN_*, TPGSR_SIDE_BATCH_CRNN, TPGSR_OVERLAP_WGRAD / TPGSR_DEFER_REDUCE) are read when the engine is
+built (CRNNEngine.__init__), nowhere else in this module."""
 from __future__ import annotations
 
 import os
@@ -222,6 +225,22 @@ class CRNNEngine(_EngineBase):
     BN_AT = (2, 4, 6)
     EARLY_CONVS = 3          # convolutions of pack group 0 = the part of the forward plan in front of the cut (TPGSR_CRNN_PACK_SPLIT=0: no cut)
 
+    def __init__(self, module: torch.nn.Module):
+        super().__init__(module)
+        # The schedule switches, read ONCE, here: _record, _record_bwd and early_final_offset() answer from these attributes, so the cut a
+        # train step builds its gradient buckets on is the cut the plans were recorded with, whatever the environment says later.
+        env = os.environ.get
+        self.overlap_wgrad = env("TPGSR_OVERLAP_WGRAD", "1") != "0"       # weight gradients on the side stream (as TSRNEngine)
+        self.defer_reduce = env("TPGSR_DEFER_REDUCE", "1") != "0"         # ... and their slab reduces batched
+        self.pack_split = env("TPGSR_CRNN_PACK_SPLIT", "1") != "0"        # training: the operands behind conv2 packed by a plan of their own
+        self.early_reduce = env("TPGSR_CRNN_EARLY_REDUCE", "1") != "0"    # the slab reduce of both BiLSTMs, conv6..conv3 behind conv3's weight gradient
+        self.bwd_split = env("TPGSR_CRNN_BWD_SPLIT", "1") != "0"          # ... and the backward pass cut into two plans there
+        # side batches of the backward pass (K.side_batch_begin): 1 = both BiLSTMs' weight gradients behind one fork and conv6..conv3's (+
+        # the early slab reduce) behind another; 2 = conv2 / conv1 as well; conv0's stays on its own (it is the tail of the pass)
+        # (default 0 since the BiLSTM layers' weight gradients are ONE launch each: with the weight-gradient stream no longer busy with ten
+        #  small GEMMs, holding conv6..conv3's back until conv3's data gradient is out only delays them -- C3 6.20 -> 6.05 ms per step)
+        self.side_batch = int(env("TPGSR_SIDE_BATCH_CRNN", "0"))
+
     def _build_layers(self):
         self.convs, self.bns = [], {}
         for i in range(7):
@@ -263,9 +282,9 @@ class CRNNEngine(_EngineBase):
         fwd_b, pack_late = Plan("crnn_fwd_b"), Plan("crnn_pack_late")
         # weight gradients on the side stream + one batched slab reduce, as in TSRNEngine (every buffer a weight-gradient
         # launch reads -- ds{i}, saved activations, the LSTM gate gradients after the time loop -- is written once per pass)
-        bwd, bwd_b = K.backward_plan("crnn_bwd"), K.backward_plan("crnn_bwd_b")
+        bwd, bwd_b = (K.backward_plan(n, overlap=self.overlap_wgrad, defer=self.defer_reduce) for n in ("crnn_bwd", "crnn_bwd_b"))
         fwd.final = bwd.final = bwd_b.final = dgp.final = pack.final = fwd_b.final = pack_late.final = final
-        split_pack = training and os.environ.get("TPGSR_CRNN_PACK_SPLIT", "1") != "0"
+        split_pack = training and self.pack_split
         self._cur_ws, self._wg_idx = ws, 0
         for bn in self._bn_layers:
             bn.use(ws)
@@ -282,8 +301,8 @@ class CRNNEngine(_EngineBase):
                 # the pass is recorded as TWO plans, cut behind the early slab reduce: every gradient from conv3 to the end of the
                 # parameter arena (both BiLSTMs, conv6..conv3, bn6 / bn4: 95.6 % of it) is final there, and a data-parallel train step
                 # launches that bucket's all-reduce between the two (backward(..., after_early=...)) under the rest of the pass
-                self._record_bwd(N, ws, cut_to=bwd_b if os.environ.get("TPGSR_CRNN_BWD_SPLIT", "1") != "0" else None)
-                if K.deferring():
+                self._record_bwd(N, ws, cut_to=bwd_b if self.bwd_split else None)
+                if self.defer_reduce:
                     K.flush_wgrad_reduces()
                 K._REC.join()
             with recording(dgp), K.conv_terms(K.terms_for("tpg", "bwd")):   # d gray: only later cascade stages ask for it
@@ -346,11 +365,7 @@ class CRNNEngine(_EngineBase):
         K.pad_channels(K.DynPtr("dlogits"), N * T, self.nclass, cp, de)
         cnn_loader = dict(in_act="relu", **self.bns[6].loader)
         fz = None                                 # BatchNorm-backward sums already left behind by the producer of `da`
-        # side batches (K.side_batch_begin): 1 = both BiLSTMs' weight gradients behind one fork and conv6..conv3's (+ the early slab
-        # reduce) behind another; 2 = conv2 / conv1 as well; conv0's stays on its own (it is the tail of the pass)
-        # (default 0 since the BiLSTM layers' weight gradients are ONE launch each: with the weight-gradient stream no longer busy with ten
-        #  small GEMMs, holding conv6..conv3's back until conv3's data gradient is out only delays them -- C3 6.20 -> 6.05 ms per step)
-        sbl = int(os.environ.get("TPGSR_SIDE_BATCH_CRNN", "0"))
+        sbl = self.side_batch                     # (levels: see __init__)
         sb = K.side_batch_begin() if sbl >= 1 else False
         for j in (1, 0):
             L = self.lstm[j]
@@ -398,7 +413,7 @@ class CRNNEngine(_EngineBase):
                 else:
                     xin, ld = t[f"s{pi}"], (dict(in_act="relu", **pbn.loader) if pbn else dict(in_act="relu"))
             conv.wgrad(N, h, w, xin, ds, loader=ld)
-            if i == 3 and K.deferring() and os.environ.get("TPGSR_CRNN_EARLY_REDUCE", "1") != "0":
+            if i == 3 and self.defer_reduce and self.early_reduce:
                 # the slab reduce of everything recorded so far (both BiLSTMs, conv6..conv3: 92 % of the parameters) goes out now and
                 # overlaps with the rest of this backward pass; the reduce at the end of the plan -- on the step's critical tail,
                 # nothing is left to hide it -- then only covers conv2..conv0
@@ -469,8 +484,9 @@ class CRNNEngine(_EngineBase):
 
     def early_final_offset(self) -> Optional[int]:
         """offset (floats, in this network's gradient arena) from which on the gradients are final after the FIRST backward plan --
-        None when the pass is recorded as one plan (TPGSR_CRNN_EARLY_REDUCE=0 / no deferred reduces)"""
-        if "0" in (os.environ.get("TPGSR_CRNN_EARLY_REDUCE", "1"), os.environ.get("TPGSR_DEFER_REDUCE", "1"), os.environ.get("TPGSR_CRNN_BWD_SPLIT", "1")):
+        None when the pass is recorded as one plan (built with TPGSR_CRNN_EARLY_REDUCE=0 / TPGSR_CRNN_BWD_SPLIT=0 / no deferred reduces:
+        the condition under which _record_bwd cuts)"""
+        if not (self.defer_reduce and self.early_reduce and self.bwd_split):
             return None
         return self.arena.layout()[0][self.EARLY_FINAL_FROM]
 

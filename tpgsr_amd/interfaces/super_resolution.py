@@ -4,7 +4,8 @@ no LMDB loaders, logging, evaluation or checkpoint rotation -- SURVEY.md section
 `TSRNTrainStep` is config C2 (`--arch tsrn`): sr = model(lr); loss = ImageLoss(sr, hr).mean()*100; zero_grad;
 backward; clip_grad_norm_(model, 0.25); Adam(lr 1e-3, betas (0.5, 0.999)).  The whole step is a fixed sequence of
 HIP kernel launches on one stream (forward plan, loss, backward plan, optional RCCL all-reduce of the flat gradient
-arena, clip + Adam), so it can be captured once into a hipGraph and replayed (`capture()`)."""
+arena, clip + Adam), so it can be captured once into a hipGraph and replayed (`capture()`).  `TPGSRTrainStep` is the cascade (C3-C5).
+Both are a `_phase_a` on the skeleton of `_TrainStep`; their image criterion is one `ImageCriterion`."""
 import os
 from typing import Optional
 
@@ -31,50 +32,60 @@ def _warn_hw_queues(collective: bool):
         nq = 4
     if collective and not K.DRYRUN and nq < 8:
         import warnings
+        # (stacklevel: this function <- _TrainStep.__init__ <- the subclass's constructor <- its caller, whom the warning is for)
         warnings.warn("tpgsr_amd: a gradient exchange is on but GPU_MAX_HW_QUEUES is %s (< 8): the train step's streams and RCCL's will "
                       "share hardware queues (~0.9 ms per step on MI355X).  Export GPU_MAX_HW_QUEUES=8 before the process starts "
-                      "(INTEGRATION.md section 4)." % os.environ.get("GPU_MAX_HW_QUEUES", "unset (HIP default 4)"), RuntimeWarning, stacklevel=3)
+                      "(INTEGRATION.md section 4)." % os.environ.get("GPU_MAX_HW_QUEUES", "unset (HIP default 4)"), RuntimeWarning, stacklevel=4)
 
 
 IMAGE_CRITS = ("image_loss", "mse", "l1", "l1_charbonnier")
 CHARBONNIER_EPS = 1e-6      # L1_Charbonnier_loss.eps (model/lapsrn.py:131)
 
 
-def _image_crit(who: str, image_crit: str, gradient, loss_weight):
-    """the image criterion of a train step (interfaces/base.py:332-368) -> (gradient, w0, w1) of its kernels: "image_loss" =
-    ImageLoss(gradient, loss_weight) of tsrn / tsrn_tl_cascade; "mse" = nn.MSELoss() of srres / vdsr / srresnet_tl / srcnn_tl / vdsr_tl (the
-    image-loss kernels with the gradient term off and w0 = 1); "l1" = nn.L1Loss() of rdn / rdn_tl / esrgan (tpgsr_l1_loss_fwd / _bwd);
-    "l1_charbonnier" = lapsrn.L1_Charbonnier_loss() of lapsrn (interfaces/base.py:351-353; tpgsr_charbonnier_loss_fwd / _bwd): a SUM over
-    the elements, so `.mean()` of the scalar changes nothing and the step's loss is 100 times that sum"""
-    if image_crit not in IMAGE_CRITS:
-        raise ValueError(f"{who}: image_crit={image_crit!r}, expected 'image_loss', 'mse', 'l1' or 'l1_charbonnier'")
-    if image_crit != "image_loss":
-        return False, 1.0, 0.0
-    return bool(gradient), float(loss_weight[0]), float(loss_weight[1])
+class ImageCriterion:
+    """the image criterion of a train step (interfaces/base.py:332-368) on its kernels: "image_loss" = ImageLoss(gradient, loss_weight) of
+    tsrn / tsrn_tl_cascade; "mse" = nn.MSELoss() of srres / vdsr / srresnet_tl / srcnn_tl / vdsr_tl (the image-loss kernels with the
+    gradient term off and w0 = 1); "l1" = nn.L1Loss() of rdn / rdn_tl / esrgan (tpgsr_l1_loss_fwd / _bwd); "l1_charbonnier" =
+    lapsrn.L1_Charbonnier_loss() of lapsrn (interfaces/base.py:351-353; tpgsr_charbonnier_loss_fwd / _bwd): a SUM over the elements, so
+    `.mean()` of the scalar changes nothing and the step's loss is 100 times that sum.  `who` prefixes the refusal of an unknown name."""
+
+    def __init__(self, who: str, image_crit: str, gradient, loss_weight):
+        if image_crit not in IMAGE_CRITS:
+            raise ValueError(f"{who}: image_crit={image_crit!r}, expected 'image_loss', 'mse', 'l1' or 'l1_charbonnier'")
+        self.name = image_crit
+        self.gradient, self.w0, self.w1 = (bool(gradient), float(loss_weight[0]), float(loss_weight[1])) if image_crit == "image_loss" \
+            else (False, 1.0, 0.0)
+
+    def value(self, sr, hr, part, loss):
+        """criterion(sr, hr).mean() * 100 -> the device scalar `loss` (two launches on the current stream)"""
+        if self.name == "l1_charbonnier":      # a sum, not a mean: the finalize divides by 1
+            K.charbonnier_loss_fwd(sr, hr, sr.numel(), CHARBONNIER_EPS, part, _NBLK_IMG)
+            K.image_loss_finalize(part, _NBLK_IMG, 1, 0, self.w0 * 100.0, 0.0, loss)
+            return
+        N, C, H2, W2 = sr.shape
+        if self.name == "l1":
+            K.l1_loss_fwd(sr, hr, sr.numel(), part, _NBLK_IMG)
+        else:
+            K.image_loss_fwd(sr, hr, N, C, H2, W2, self.gradient, part, _NBLK_IMG)
+        n_gp = N * min(C, 3) * H2 * W2 if self.gradient else 0
+        K.image_loss_finalize(part, _NBLK_IMG, sr.numel(), n_gp, self.w0 * 100.0, self.w1 * 100.0, loss)
+
+    def grad(self, sr, hr, dloss, dsr):
+        """d (criterion(sr, hr).mean() * dloss) / d sr -> dsr"""
+        if self.name == "l1_charbonnier":
+            K.charbonnier_loss_bwd(sr, hr, dloss, sr.numel(), CHARBONNIER_EPS, self.w0, dsr)
+        elif self.name == "l1":
+            K.l1_loss_bwd(sr, hr, dloss, sr.numel(), self.w0, dsr)
+        else:
+            N, C, H2, W2 = sr.shape
+            K.image_loss_bwd(sr, hr, dloss, N, C, H2, W2, self.gradient, self.w0, self.w1, dsr)
 
 
-def _image_crit_value(image_crit, sr, hr, N, C, H2, W2, gradient, w0, w1, part, loss):
-    """criterion(sr, hr).mean() * 100 -> the device scalar `loss` (two launches on the current stream)"""
-    if image_crit == "l1_charbonnier":      # a sum, not a mean: the finalize divides by 1
-        K.charbonnier_loss_fwd(sr, hr, sr.numel(), CHARBONNIER_EPS, part, _NBLK_IMG)
-        K.image_loss_finalize(part, _NBLK_IMG, 1, 0, w0 * 100.0, 0.0, loss)
-        return
-    if image_crit == "l1":
-        K.l1_loss_fwd(sr, hr, sr.numel(), part, _NBLK_IMG)
-    else:
-        K.image_loss_fwd(sr, hr, N, C, H2, W2, gradient, part, _NBLK_IMG)
-    n_gp = N * min(C, 3) * H2 * W2 if gradient else 0
-    K.image_loss_finalize(part, _NBLK_IMG, sr.numel(), n_gp, w0 * 100.0, w1 * 100.0, loss)
-
-
-def _image_crit_grad(image_crit, sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, dsr):
-    """d (criterion(sr, hr).mean() * dloss) / d sr -> dsr"""
-    if image_crit == "l1_charbonnier":
-        K.charbonnier_loss_bwd(sr, hr, dloss, sr.numel(), CHARBONNIER_EPS, w0, dsr)
-    elif image_crit == "l1":
-        K.l1_loss_bwd(sr, hr, dloss, sr.numel(), w0, dsr)
-    else:
-        K.image_loss_bwd(sr, hr, dloss, N, C, H2, W2, gradient, w0, w1, dsr)
+def _channel_prefix(src, dst):
+    """dst (N, Cs, H, W) = src[:, :Cs] of a contiguous NCHW batch: one strided-copy launch (rows = samples)"""
+    N, C, H, W = src.shape
+    Cs = dst.shape[1]
+    K.copy_strided(src, C * H * W, 0, dst, Cs * H * W, 0, N, Cs * H * W)
 
 
 def _sr_scale(who, modules) -> int:
@@ -101,7 +112,118 @@ def _refuse_exchange_with_functional_engine(who, modules, advice):
                                       f"(DESIGN section 7).  {advice}")
 
 
-class TSRNTrainStep:
+class _TrainStep:
+    """What the two train steps share: the pooled arena and its Adam, the gradient exchange, the order of one step (bind, _phase_a, exchange,
+    _phase_b) and its capture into hipGraphs.  A subclass supplies `_buffers`, `_phase_a(lr, hr, ...)` (zero_grad + forward + loss + backward:
+    everything before the exchange), `_exchanger` (the buckets of the flat gradient buffer), `_check_ready` (its train-mode check) and
+    `step` with its own signature around `_step`."""
+    who = None                  # prefix of the subclass's refusals
+    frozen = ()                 # modules outside the pool that a step binds and a start-up broadcast covers (the cascade's teacher)
+    _overlap_exchange = True    # False while capture() records: the all-reduce stays between the graphs (the cascade's _phase_a reads it)
+
+    def __init__(self, sr_modules, other_modules, advice, gradient, loss_weight, lr, betas, max_norm, process_group, world_size,
+                 force_collectives, precision, image_crit):
+        """sr_modules: the SR network(s) -- clipped at max_norm, and what `advice` ends the refusal of an exchange about; other_modules:
+        what else the optimiser trains (the cascade's students, not clipped)"""
+        # arithmetic policy of the step's GEMMs (kernels.py): `precision`, else an explicit TPGSR_CONV_PREC / set_conv_prec, else "x2" --
+        # the benchmarked policy, gated at full size against the oracle on both north_star gates (tests/test_policy_x2*_gpu.py)
+        self.precision = K.train_step_policy(precision)
+        self.collective = world_size > 1 or bool(force_collectives)   # force: drive RCCL at world size 1 too (tests)
+        _warn_hw_queues(self.collective)
+        self.image_crit = image_crit
+        self.crit = ImageCriterion(self.who, image_crit, gradient, loss_weight)
+        if self.collective:
+            _refuse_exchange_with_functional_engine(self.who, sr_modules, advice)
+        mods = sr_modules + other_modules
+        # one flat parameter / gradient buffer: SR net(s) first, then the students = the order their gradients become final
+        self.pool = ArenaPool(mods)
+        self.opt = FusedAdam(mods, lr=lr, betas=betas, clip_modules=sr_modules, max_norm=max_norm, pool=self.pool)
+        self.pg, self.world = process_group, world_size
+        self._graph = self._graph_b = None
+        self._static = None
+        self._exch = None
+
+    def _exchange(self):
+        """RCCL all-reduce (sum) of the flat gradient buffer over xGMI, then the 1/world average: `_exchanger()`'s buckets -- ONE for the
+        single-network step; SR nets | students, a student cut in two, for the cascade, all but the last launched inside its backward pass"""
+        if self.collective:
+            self._exchanger().finish()
+
+    def _phase_b(self):
+        self.opt.step()
+
+    def _bind(self, device):
+        self.pool.bind(device)
+        for m in self.frozen:
+            m._engine().bind(device)
+
+    def _step(self, lr_img, hr_img, *labels):
+        """one training step; `labels`: what the subclass's `step` takes besides the two batches, handed on to its _check_ready and _phase_a"""
+        self._check_ready(*labels)
+        with K.policy(self.precision):
+            self._bind(lr_img.device)
+            loss = self._phase_a(lr_img, hr_img, *labels)
+            self._exchange()
+            self._phase_b()
+        return loss
+
+    def broadcast_parameters(self, src: int = 0):
+        """DDP start-up: every rank adopts rank `src`'s parameters (one flat broadcast, + the arena of each frozen module) and BN buffers."""
+        if self.world > 1:
+            self._bind(next(self.pool.modules[0].parameters()).device)
+            mods = self.pool.modules + list(self.frozen)
+            broadcast_state(self.pool.flat, [b for m in mods for b in m.buffers()], src, self.pg)
+            for m in self.frozen:
+                broadcast_state(m._engine().arena.flat, [], src, self.pg)
+            for m in mods:      # the arenas changed behind the parameters' version counters
+                m._engine()._kernel_writes += 1
+
+    # -- hipGraph replay ----------------------------------------------------------------------------------------
+    def capture(self, lr_img: torch.Tensor, hr_img: torch.Tensor, warmup: int = 2):
+        """Capture the step on static input buffers: one graph for world_size 1; two graphs (before / after the RCCL
+        all-reduce, which stays an ordinary stream-ordered call between them) for world_size > 1.
+        `replay(lr, hr)` copies new data into the static buffers and launches the graph(s)."""
+        self._lr, self._hr = lr_img.clone(), hr_img.clone()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self.step(self._lr, self._hr)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        ga = torch.cuda.CUDAGraph()
+        self._overlap_exchange = False       # the all-reduce stays between the two graphs ...
+        try:
+            with torch.cuda.graph(ga), K.policy(self.precision):
+                self._graph_loss = self._phase_a(self._lr, self._hr)
+                if self.world == 1:
+                    self._phase_b()
+        finally:
+            self._overlap_exchange = True    # ... and eager step() calls after a capture overlap it with the backward pass again
+        self._graph, self._graph_b = ga, None
+        if self.world > 1:
+            gb = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gb):
+                self._phase_b()
+            self._graph_b = gb
+        return ga
+
+    def replay(self, lr_img: Optional[torch.Tensor] = None, hr_img: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if lr_img is not None:
+            self._lr.copy_(lr_img)
+        if hr_img is not None:
+            self._hr.copy_(hr_img)
+        self._graph.replay()
+        if self._graph_b is not None:
+            self._exchange()
+            self._graph_b.replay()
+        # the captured Adam rewrote the pooled arena behind every version counter: eval-mode forwards after this must re-pack (ADVICE round 4)
+        for m in self.pool.modules:
+            m._engine().invalidate_packed()
+        return self._graph_loss
+
+
+class TSRNTrainStep(_TrainStep):
     """The single-network step: `--arch tsrn` (config C2) with the defaults, and the `else:` branch of the reference's train loop
     (interfaces/super_resolution.py:409-424) for the prior-free baselines -- any module whose `_engine()` follows the SR engine protocol:
         SRTrainStep(srresnet.SRResNet(mask=True), image_crit="mse")          # train_SRResNet.sh
@@ -109,31 +231,20 @@ class TSRNTrainStep:
         SRTrainStep(vdsr.VDSR(), image_crit="mse", channels=3)
         SRTrainStep(lapsrn.LapSRN(scale_factor=4), image_crit="l1_charbonnier", channels=3)      # --arch lapsrn, no --mask
         SRTrainStep(esrgan.RRDBNet(scale_factor=4), image_crit="l1", channels=3)                 # --arch esrgan, no --mask
-    image_crit: the criterion interfaces/base.py:332-347 pairs with the architecture (`_image_crit` above).  channels: the reference's
+    image_crit: the criterion interfaces/base.py:332-347 pairs with the architecture (`ImageCriterion` above).  channels: the reference's
     channel_num -- the step feeds lr[:, :channels] and compares with hr[:, :channels] (:410-416); the prefix is gathered by a kernel
     launch (tpgsr_copy_strided), so capture() / replay() work on it."""
+    who = "TSRNTrainStep"
 
     def __init__(self, model, gradient=True, loss_weight=(1.0, 1e-4), lr=1e-3, betas=(0.5, 0.999), max_norm=0.25,
                  process_group=None, world_size: int = 1, force_collectives: bool = False, precision: Optional[str] = None,
                  image_crit: str = "image_loss", channels: Optional[int] = None):
         self.model = model
-        self.image_crit = image_crit
         if channels is not None and int(channels) < 1:
             raise ValueError(f"TSRNTrainStep: channels={channels!r}, expected None or a positive plane count")
         self.channels = None if channels is None else int(channels)
-        # arithmetic policy of the step's GEMMs (kernels.py): `precision`, else an explicit TPGSR_CONV_PREC / set_conv_prec, else "x2"
-        self.precision = K.train_step_policy(precision)
-        self.collective = world_size > 1 or bool(force_collectives)   # force: drive RCCL at world size 1 too (tests)
-        _warn_hw_queues(self.collective)
-        self.gradient, self.w0, self.w1 = _image_crit("TSRNTrainStep", image_crit, gradient, loss_weight)
-        if self.collective:
-            _refuse_exchange_with_functional_engine("TSRNTrainStep", [model], "Train the baseline backbones on one GPU per process group of size 1.")
-        self.pool = ArenaPool([model])
-        self.opt = FusedAdam([model], lr=lr, betas=betas, clip_modules=[model], max_norm=max_norm, pool=self.pool)
-        self.pg, self.world = process_group, world_size
-        self._graph = None
-        self._static = None
-        self._exch = None
+        super().__init__([model], [], "Train the baseline backbones on one GPU per process group of size 1.", gradient, loss_weight, lr, betas,
+                         max_norm, process_group, world_size, force_collectives, precision, image_crit)
 
     # -- one step as plain launches ---------------------------------------------------------------------------
     def _buffers(self, lr_img):
@@ -152,13 +263,6 @@ class TSRNTrainStep:
                 self._static.update(lr_c=torch.empty(N, Cs, H, W, device=dev), hr_c=torch.empty(N, Cs, s * H, s * W, device=dev))
         return self._static
 
-    @staticmethod
-    def _prefix(src, dst):
-        """dst (N, Cs, H, W) = src[:, :Cs] of a contiguous NCHW batch: one strided-copy launch (rows = samples)"""
-        N, C, H, W = src.shape
-        Cs = dst.shape[1]
-        K.copy_strided(src, C * H * W, 0, dst, Cs * H * W, 0, N, Cs * H * W)
-
     def _phase_a(self, lr_img, hr_img):
         """zero_grad + forward + loss + backward (everything before the gradient exchange)"""
         model = self.model
@@ -170,18 +274,17 @@ class TSRNTrainStep:
         self.opt.zero_grad()
         hr = hr_img.contiguous()
         if "lr_c" in st:
-            self._prefix(lr_img.contiguous(), st["lr_c"])
-            self._prefix(hr, st["hr_c"])
-            lr_img, hr, C = st["lr_c"], st["hr_c"], st["lr_c"].shape[1]
+            _channel_prefix(lr_img.contiguous(), st["lr_c"])
+            _channel_prefix(hr, st["hr_c"])
+            lr_img, hr = st["lr_c"], st["hr_c"]
         sr = eng.forward(lr_img, True)
-        H2, W2 = s * H, s * W
         # the loss VALUE is for the caller's log (the gradient below does not read it): its pass over sr / hr and the single-wave finalize run
         # on the auxiliary stream next to the backward pass, not in front of it
         main, aux = K.current_stream(), K.aux_stream(lr_img.device)
         K.order(aux, main)
         with K.stream_ctx(aux):
-            _image_crit_value(self.image_crit, sr, hr, N, C, H2, W2, self.gradient, self.w0, self.w1, st["part"], st["loss"])
-        _image_crit_grad(self.image_crit, sr, hr, st["dloss"], N, C, H2, W2, self.gradient, self.w0, self.w1, st["dsr"])
+            self.crit.value(sr, hr, st["part"], st["loss"])
+        self.crit.grad(sr, hr, st["dloss"], st["dsr"])
         eng.backward(tuple(lr_img.shape), sr, st["dsr"])
         K.order(main, aux)
         self.last_sr = sr
@@ -194,72 +297,13 @@ class TSRNTrainStep:
                                            scale_fn=lambda flat, _s: K.scale_(flat, flat.numel(), inv), force=self.collective)
         return self._exch
 
-    def _exchange(self):
-        """ONE flat bucket: RCCL all-reduce (sum) of the gradient arena over xGMI, then the 1/world average"""
-        if self.collective:
-            self._exchanger().finish()
-
-    def _phase_b(self):
-        self.opt.step()
+    def _check_ready(self):
+        if not self.model.training:
+            raise RuntimeError("TSRNTrainStep.step needs model.train()")
 
     def step(self, lr_img: torch.Tensor, hr_img: torch.Tensor) -> torch.Tensor:
         """Returns the (device) loss scalar = ImageLoss(sr, hr).mean() * 100 of this step (this rank's shard)."""
-        if not self.model.training:
-            raise RuntimeError("TSRNTrainStep.step needs model.train()")
-        with K.policy(self.precision):
-            self.pool.bind(lr_img.device)
-            loss = self._phase_a(lr_img, hr_img)
-            self._exchange()
-            self._phase_b()
-        return loss
-
-    def broadcast_parameters(self, src: int = 0):
-        """DDP start-up: every rank adopts rank `src`'s parameters and BN buffers (one flat broadcast + buffers)."""
-        if self.world > 1:
-            self.pool.bind(next(self.model.parameters()).device)
-            broadcast_state(self.pool.flat, self.model.buffers(), src, self.pg)
-            self.model._engine()._kernel_writes += 1      # the arena changed behind the parameters' version counters
-
-    # -- hipGraph replay ----------------------------------------------------------------------------------------
-    def capture(self, lr_img: torch.Tensor, hr_img: torch.Tensor, warmup: int = 2):
-        """Capture the step on static input buffers: one graph for world_size 1; two graphs (before / after the RCCL
-        all-reduce, which stays an ordinary stream-ordered call between them) for world_size > 1.
-        `replay(lr, hr)` copies new data into the static buffers and launches the graph(s)."""
-        self._lr = lr_img.clone()
-        self._hr = hr_img.clone()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.step(self._lr, self._hr)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        ga = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(ga), K.policy(self.precision):
-            self._graph_loss = self._phase_a(self._lr, self._hr)
-            if self.world == 1:
-                self._phase_b()
-        self._graph = ga
-        self._graph_b = None
-        if self.world > 1:
-            gb = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gb):
-                self._phase_b()
-            self._graph_b = gb
-        return ga
-
-    def replay(self, lr_img: Optional[torch.Tensor] = None, hr_img: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if lr_img is not None:
-            self._lr.copy_(lr_img)
-        if hr_img is not None:
-            self._hr.copy_(hr_img)
-        self._graph.replay()
-        if self._graph_b is not None:
-            self._exchange()
-            self._graph_b.replay()
-        # the captured Adam rewrote the arena behind every version counter: an eval-mode forward after this must re-pack (ADVICE round 4)
-        self.model._engine().invalidate_packed()
-        return self._graph_loss
+        return self._step(lr_img, hr_img)
 
 
 SRTrainStep = TSRNTrainStep      # the name the prior-free baselines are trained under (same class)
@@ -291,13 +335,14 @@ class _ParseCrnnFn(torch.autograd.Function):
         return din
 
 
-class TPGSRTrainStep:
+class TPGSRTrainStep(_TrainStep):
     """Configs C3-C5 (`--arch tsrn_tl_cascade --use_distill`), interfaces/super_resolution.py:295-406 + :419-424:
     teacher CRNN(HR) -> q (no grad); per stage: student CRNN(prev image) -> softmax p -> distill loss*100 -> prior
     (N,37,1,26) with samples [0, N//4) zeroed -> TSRN_TL(LR, prior) -> image loss*100; sum; backward through every
     stage (the student receives gradient from the distill loss AND through the prior; later stages back-propagate
     through parse_crnn_data into the previous SR image); clip each SR net at 0.25 (students are not clipped); ONE Adam
     over SR nets + students."""
+    who = "TPGSRTrainStep"
 
     def __init__(self, sr_models, students, teacher, stu_iter=1, sr_share=True, tpg_share=False, gradient=True,
                  loss_weight=(1.0, 1e-4), lr=1e-3, betas=(0.5, 0.999), max_norm=0.25, process_group=None, world_size=1,
@@ -311,35 +356,17 @@ class TPGSRTrainStep:
         self.use_label, self.use_distill = bool(use_label), bool(use_distill)
         if not (self.use_label or self.use_distill):
             raise ValueError("TPGSRTrainStep: the cascade branch trains the text-prior generator through --use_distill and / or --use_label")
-        # arithmetic policy of the step's GEMMs (kernels.py): `precision`, else an explicit TPGSR_CONV_PREC / set_conv_prec, else "x2" --
-        # the benchmarked policy, gated at full size against the oracle on both north_star gates (tests/test_policy_x2*_gpu.py)
-        self.precision = K.train_step_policy(precision)
-        # the image criterion (interfaces/base.py:355-368): "image_loss" = ImageLoss(gradient, loss_weight) of tsrn / tsrn_tl_cascade;
-        # "mse" = nn.MSELoss() of srresnet_tl / srcnn_tl / vdsr_tl (the image-loss kernels with the gradient term off and w0 = 1);
-        # "l1" = nn.L1Loss() of rdn_tl (tpgsr_l1_loss_fwd / _bwd).  All three: .mean() * 100, value computed on the teacher's stream
-        self.gradient, self.w0, self.w1 = _image_crit("TPGSRTrainStep", image_crit, gradient, loss_weight)
-        self.image_crit = image_crit
-        self.collective = world_size > 1 or bool(force_collectives)   # force: drive RCCL at world size 1 too (tests)
-        _warn_hw_queues(self.collective)
         self.sr = list(sr_models) if isinstance(sr_models, (list, tuple)) else [sr_models]
         self.stu = list(students) if isinstance(students, (list, tuple)) else [students]
         self.teacher = teacher
+        self.frozen = [teacher]
         if hasattr(teacher, "_engine") and all(teacher is not m for m in self.stu):
             teacher._engine().role = "teacher"      # arithmetic policy: its output is a soft target only (kernels.terms_for)
         self.stu_iter, self.sr_share, self.tpg_share = stu_iter, sr_share, tpg_share
-        if self.collective:
-            _refuse_exchange_with_functional_engine("TPGSRTrainStep", self.sr, "Train the _TL baseline backbones on one GPU per process group of size 1.")
-        mods = self.sr + self.stu
-        # one flat parameter / gradient buffer: SR net(s) first, then the students = the order their gradients become final
-        self.pool = ArenaPool(mods)
-        self.opt = FusedAdam(mods, lr=lr, betas=betas, clip_modules=self.sr, max_norm=max_norm, pool=self.pool)
-        self.pg, self.world = process_group, world_size
-        self._static = None
-        self._graph = None
+        # the image criterion (`ImageCriterion`): .mean() * 100, its value computed on the teacher's stream
+        super().__init__(self.sr, self.stu, "Train the _TL baseline backbones on one GPU per process group of size 1.", gradient, loss_weight,
+                         lr, betas, max_norm, process_group, world_size, force_collectives, precision, image_crit)
         self._dbg = {}
-        self._exch = None
-        self._early_bucket = None          # index of the text-prior generator's early gradient bucket (see _exchanger)
-        self._overlap_exchange = True      # False while capturing hipGraphs (the all-reduce stays between the graphs)
         # The SR network's backward plan does not join the weight-gradient stream at its end (the student's backward pass starts right
         # away); _join_side() orders the main stream after it before clip + Adam.  With a gradient exchange the SR bucket is launched
         # FROM the weight-gradient stream (its tail is ordered after every gradient of the SR network: the weight gradients and their
@@ -461,7 +488,7 @@ class TPGSRTrainStep:
                     K.ctc_loss(logits, 26 * 37, 37, ctc[0], ctc[1], ctc[2], None, N, 26, 37, 0, 0.0, st["ctc_nll"][i], None, False, ctc[4])
                     if not K.DRYRUN:
                         st["l_sem"][i].add_((st["ctc_nll"][i] * ctc[3]).mean())
-                _image_crit_value(self.image_crit, sr, hr, N, C, H2, W2, self.gradient, self.w0, self.w1, st["part_img"][i], st["l_img"][i])
+                self.crit.value(sr, hr, st["part_img"][i], st["l_img"][i])
                 if self.ssim_loss:      # loss_img += (1 - ssim.mean()) * 10: the mean by tpgsr_ssim, the scalar arithmetic by three ATen launches
                     K.ssim(sr, hr, st["ssim_win"], 11, N, C, H2, W2, st["ssim_part"], 256, st["ssim_out"])
                     if not K.DRYRUN:
@@ -480,7 +507,7 @@ class TPGSRTrainStep:
         for i in range(self.stu_iter - 1, -1, -1):
             stu = self.stu[0 if self.tpg_share else i]
             srm = self.sr[0 if self.sr_share else i]
-            _image_crit_grad(self.image_crit, srs[i], hr, st["dloss"], N, C, H2, W2, self.gradient, self.w0, self.w1, st["dsr"][i])
+            self.crit.grad(srs[i], hr, st["dloss"], st["dsr"][i])
             if self.ssim_loss:             # d/d sr of (1 - mean ssim) * 10, added to the first three channels of the image-loss gradient
                 K.ssim_bwd(srs[i], hr, st["ssim_win"], 11, N, C, H2, W2, st["ssim_gm"], None, -10.0 / (N * min(C, 3) * H2 * W2), st["dsr"][i], True)
             if i < self.stu_iter - 1:      # gradient arriving through the next stage's parse_crnn_data
@@ -552,7 +579,6 @@ class TPGSRTrainStep:
                     self._buckets[("sr" if any(m is q for q in self.sr) else "rest", id(m))] = len(bounds)
                     bounds.append((prev_end, b))
                 prev_end = b
-            self._early_bucket = next((v for (k, _), v in self._buckets.items() if k == "early"), None)
             self._exch = GradientExchanger(self.pool.grad, bounds, self.pg,
                                            scale_fn=lambda flat, _s: K.scale_(flat, flat.numel(), inv), force=self.collective)
         return self._exch
@@ -581,11 +607,6 @@ class TPGSRTrainStep:
         with K.stream_ctx(side):
             self._exchanger().launch(b)
 
-    def _exchange(self):
-        """buckets of ONE flat buffer (SR nets | students, the single student cut in two); all but the last were launched inside the backward pass"""
-        if self.collective:
-            self._exchanger().finish()
-
     def _join_side(self, device):
         if K.DRYRUN:
             return
@@ -595,75 +616,17 @@ class TPGSRTrainStep:
         # and the loss value is computed there (always: with and without the deferred join)
         K.order(K.current_stream(), K.aux_stream(device))
 
-    def _phase_b(self):
-        self.opt.step()
-
-    def broadcast_parameters(self, src: int = 0):
-        """DDP start-up: every rank adopts rank `src`'s parameters (one flat broadcast) and BN buffers."""
-        if self.world > 1:
-            dev = next(self.sr[0].parameters()).device
-            self.pool.bind(dev)
-            self.teacher._engine().bind(dev)
-            bufs = [b for m in self.pool.modules + [self.teacher] for b in m.buffers()]
-            broadcast_state(self.pool.flat, bufs, src, self.pg)
-            broadcast_state(self.teacher._engine().arena.flat, [], src, self.pg)
-            for m in self.pool.modules + [self.teacher]:      # the arenas changed behind the parameters' version counters
-                m._engine()._kernel_writes += 1
-
-    def step(self, lr_img, hr_img, labels=None):
-        for m in self.sr + self.stu:
+    def _check_ready(self, labels):
+        for m in self.pool.modules:      # (the SR nets and the students)
             if not m.training:
                 raise RuntimeError("TPGSRTrainStep.step needs the SR nets and students in train() mode")
         if self.use_label and labels is None:
             raise ValueError("TPGSRTrainStep(use_label=True).step needs labels=(label_vecs, weighted_mask, weighted_tics)")
-        with K.policy(self.precision):
-            self.pool.bind(lr_img.device)
-            self.teacher._engine().bind(lr_img.device)
-            loss = self._phase_a(lr_img, hr_img, labels)
-            self._exchange()
-            self._phase_b()
+
+    def step(self, lr_img, hr_img, labels=None):
+        loss = self._step(lr_img, hr_img, labels)
         self._mark("optimiser")
         return loss
-
-    def capture(self, lr_img, hr_img, warmup=2):
-        self._lr, self._hr = lr_img.clone(), hr_img.clone()
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):
-                self.step(self._lr, self._hr)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        ga = torch.cuda.CUDAGraph()
-        self._overlap_exchange = False       # the all-reduce stays between the two graphs ...
-        try:
-            with torch.cuda.graph(ga), K.policy(self.precision):
-                self._graph_loss = self._phase_a(self._lr, self._hr)
-                if self.world == 1:
-                    self._phase_b()
-        finally:
-            self._overlap_exchange = True    # ... and eager step() calls after a capture overlap it with the backward pass again
-        self._graph, self._graph_b = ga, None
-        if self.world > 1:
-            gb = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gb):
-                self._phase_b()
-            self._graph_b = gb
-        return ga
-
-    def replay(self, lr_img=None, hr_img=None):
-        if lr_img is not None:
-            self._lr.copy_(lr_img)
-        if hr_img is not None:
-            self._hr.copy_(hr_img)
-        self._graph.replay()
-        if self._graph_b is not None:
-            self._exchange()
-            self._graph_b.replay()
-        # the captured Adam rewrote the pooled arena behind every version counter: eval-mode forwards after this must re-pack
-        for m in self.pool.modules:
-            m._engine().invalidate_packed()
-        return self._graph_loss
 
 
 def parse_aster_data(imgs_input: torch.Tensor, max_len: int = 100):
@@ -744,7 +707,7 @@ class TextSREvaluator:
                 return [srm(lr, channels=Cs)], []        # (the kernel reads the channel prefix itself)
             if Cs != C:
                 lr_c = torch.empty(N, Cs, H, W, device=dev)
-                TSRNTrainStep._prefix(lr, lr_c)
+                _channel_prefix(lr, lr_c)
                 lr = lr_c
             return [srm._engine().forward(lr, False)], []
         cascade, ch, cw = lr, H, W
@@ -807,7 +770,7 @@ class TextSREvaluator:
             if sr.shape[1] > hr.shape[1] or sr.shape[1] < min(3, hr.shape[1]):
                 raise ValueError(f"TextSREvaluator: SR image has {sr.shape[1]} planes, HR {hr.shape[1]}")
             hr_m = torch.empty(hr.shape[0], sr.shape[1], hr.shape[2], hr.shape[3], device=hr.device)
-            TSRNTrainStep._prefix(hr, hr_m)
+            _channel_prefix(hr, hr_m)
         out = dict(images_sr=srs, priors=priors, psnr=calculate_psnr(sr, hr_m), ssim=self._ssim(sr, hr_m),
                    pred_sr=self.recognize(sr), pred_lr=self.recognize(images_lr), pred_hr=self.recognize(images_hr))
         if label_strs is not None:
