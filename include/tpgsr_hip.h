@@ -684,6 +684,21 @@ int tpgsr_tconv4s2_small_bwd_weight(const float* x, const float* dy, int N, int 
                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Direct 3x3, pad 1, stride 1 convolution to 1 <= Cout <= 4 channels, NHWC, no bias (csrc/conv_narrow.hip) -- EDSR's conv_output
+ * (reference model/edsr.py:57, 256 -> 3 on the HR grid), where a matrix-core tile would be 61 / 64 padding.  x [N][H][W][Cin],
+ * w [Cout][Cin][3][3] as PyTorch stores it, y / dy [N][H][W][Cout].  Cin is a multiple of 4 up to 256 (a lane of the wave owns four
+ * channels); anything else, a null pointer or N H W >= 2^27 is refused before a launch.  Plain fp32 fused multiply-adds in a fixed order
+ * (no atomics, bitwise reproducible; the arithmetic policy of the matrix-core routes does not apply).  16-byte accesses when the
+ * pointers are 16-byte aligned, element by element otherwise.  Nothing outside the outputs is written.
+ * _bwd_weight writes partial [nblk][Cout Cin 9] in w's element order (workgroup b sums its range of pixels in order; workgroups behind
+ * the last pixel write zeros), finished by tpgsr_reduce_partials(partial, nblk, Cout Cin 9, dw, accumulate).
+ * ---------------------------------------------------------------------------------------------- */
+int tpgsr_conv3x3_narrow_fwd(const float* x, const float* w, int N, int H, int W, int Cin, int Cout, float* y, void* stream);
+int tpgsr_conv3x3_narrow_bwd_data(const float* dy, const float* w, int N, int H, int W, int Cin, int Cout, float* dx, void* stream);
+int tpgsr_conv3x3_narrow_bwd_weight(const float* x, const float* dy, int N, int H, int W, int Cin, int Cout, float* partial, int nblk,
+                                    void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Tail: out = tanh(bias + sum_kw P[h][w+kw-4][kw][co])  (model/tsrn.py:159,213), NCHW output
  * ---------------------------------------------------------------------------------------------- */
 int tpgsr_tail_shiftsum_tanh(const float* P, const float* bias, int N, int H, int W, int Co, int KS,

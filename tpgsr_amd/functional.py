@@ -774,6 +774,193 @@ def dense_block(x, weights, biases=None, slope: float = 0.2, res_scale: float = 
 DENSE_DEFAULT_FORM = "inplace"
 
 
+# ---- residual block (EDSR's _Residual_Block, model/edsr.py:18-32) -------------------------------------------------------------------
+def _wgrad3(g, x, dy, w):
+    """weight gradient of a bias-free convolution exactly as _Conv2d.backward: slabs on the side stream, reduced into the sink (-> None) or
+    into a tensor of its own"""
+    Z = K.wgrad_splits(g.M, g.K, g.Cout, geom=g)
+    part = _new(x, Z, g.K, g.Cout)
+    sw = _sink(w)
+    dw = None
+    with K.side():
+        K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, x), dy, part, None, zsplits=Z))
+        if sw is not None:
+            K.wgrad_reduce(part, None, Z, g, sw, None, layout=0, accumulate=True)
+        else:
+            dw = torch.empty_like(w)
+            K.wgrad_reduce(part, None, Z, g, dw, None, layout=0, accumulate=False)
+    return dw
+
+
+class _ResBlock(torch.autograd.Function):
+    """y = res_scale * conv2(relu(conv1(x))) + x, two bias-free 3x3 convolutions over C channels (a multiple of 4).
+
+    Forward: conv1 with ReLU in its epilogue (out_act) writes h, which is saved; conv2 writes r; one tpgsr_scaled_add forms
+    res_scale * r + x in place on r -- a rounded product, then a rounded sum: ATen's `output *= 0.1; torch.add(output, identity)`.
+
+    Backward: g = res_scale * dy by one tpgsr_scaled_add (b = NULL).  res_scale is NOT folded into conv2's packed weight (`wscale`): that
+    would scale the forward operand too -- w2 * 0.1 rounded before the products instead of the rounded product r * 0.1 -- and the
+    weight-gradient scale alone (`gscale`) would leave the data gradient unscaled.  conv2's data gradient stores dz = da * relu'(h) on its
+    way out (tpgsr_conv_args.bnb_y = h, bnb_act = RELU, bnb_store_dz, no bn_partial): h is the POST-activation map, positive exactly where
+    the pre-activation is, and the derivative at 0 is 0 (ATen's threshold_backward).  Where the launch has no such epilogue -- the fp32
+    kernels of policy f32 -- tpgsr_act_bwd runs behind the data gradient, in place.  conv1's data gradient gives T, dx = dy + T by tpgsr_add.
+    g, dz and T are the operator's own allocations, written once: the weight-gradient launches on the side stream read g / dz unordered with
+    the caller's stream moving on (a recorded plan keeps them alive)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, res_scale):
+        _chk(x, w1, w2)
+        x = _c(x)
+        N, H, W, C_ = x.shape
+        M = N * H * W
+        g = ConvGeom(N, H, W, C_, C_, 3, 3, 1, 1)
+        wf1, wd1, *_ = _pack(w1, False, 1.0)
+        wf2, wd2, *_ = _pack(w2, False, 1.0)
+        h = torch.empty_like(x)
+        K.conv_fwd(K.make_conv_args(g, x, wf1, h, out_act="relu"))
+        y = torch.empty_like(x)
+        K.conv_fwd(K.make_conv_args(g, h, wf2, y))
+        K.scaled_add(y, C_, 0, x, C_, 0, res_scale, y, C_, 0, M, C_)
+        ctx.save_for_backward(x, h, w1, w2, wd1, wd2)
+        ctx.cfg = (g, res_scale)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, h, w1, w2, wd1, wd2 = ctx.saved_tensors
+        g, res_scale = ctx.cfg
+        dy = _c(dy)
+        C_, M = g.Cin, g.M
+        dw1 = dw2 = dx = None
+        gr = torch.empty_like(dy)
+        K.scaled_add(dy, C_, 0, None, 0, 0, res_scale, gr, C_, 0, M, C_)
+        if ctx.needs_input_grad[2]:
+            dw2 = _wgrad3(g, h, gr, w2)
+        dz = torch.empty_like(dy)
+        if K.bnb_fusable(C_) and getattr(wd2, "_tpgsr_twin", None) is not None:
+            K.conv_fwd(K.make_conv_args(g.dgrad(), gr, wd2, dz, bnb=dict(y=h, act="relu", store_dz=True)))
+        else:
+            K.conv_fwd(K.make_conv_args(g.dgrad(), gr, wd2, dz))
+            K.act_bwd(h, dz, dz.numel(), "relu", dz)
+        if ctx.needs_input_grad[1]:
+            dw1 = _wgrad3(g, x, dz, w1)
+        if ctx.needs_input_grad[0]:
+            T = torch.empty_like(dy)
+            K.conv_fwd(K.make_conv_args(g.dgrad(), dz, wd1, T))
+            dx = torch.empty_like(dy)
+            K.add(dy, T, dx.numel(), dx)
+        return dx, dw1, dw2, None
+
+
+RES_FORMS = ("fused", "composed")
+
+
+def _res_block_composed(x, w1, w2, res_scale):
+    """the reference's mathematics over the existing operators"""
+    cur, skip = fork(x)
+    return scaled_add(conv2d(relu(conv2d(cur, w1, None, 1)), w2, None, 1), skip, res_scale)
+
+
+def res_block(x, w1, w2, res_scale: float = 0.1, form: Optional[str] = None):
+    """_Residual_Block (reference model/edsr.py:18-32) on an NHWC map x (N, H, W, C): res_scale * conv2(relu(conv1(x))) + x with two
+    bias-free 3x3 convolution weights [C][C][3][3].  form "fused": one operator with a hand-written backward (_ResBlock; C a multiple
+    of 4); "composed": the same mathematics over fork / conv2d / relu / scaled_add; None: RES_DEFAULT_FORM (the composed form, see there)
+    where the channel count allows it, composed otherwise.  The two forms give the same bits.  Every refusal comes before a launch."""
+    if form is not None and form not in RES_FORMS:
+        raise ValueError(f"res_block: form={form!r}, expected one of {RES_FORMS} or None")
+    if x.dim() != 4:
+        raise ValueError(f"res_block: input {tuple(x.shape)} is not (N, H, W, C)")
+    C_ = x.shape[-1]
+    for k, w in enumerate((w1, w2)):
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+            raise ValueError(f"res_block: weight {k + 1} is {tuple(w.shape)}, expected a 3x3 convolution weight [C][C][3][3]")
+        if tuple(w.shape[:2]) != (C_, C_):
+            raise ValueError(f"res_block: input has {C_} channels, weight {k + 1} is {tuple(w.shape)}")
+    fits = C_ % 4 == 0
+    if form is None:
+        form = RES_DEFAULT_FORM if fits else "composed"
+    elif form == "fused" and not fits:
+        raise ValueError(f"res_block: the fused form takes a channel count that is a multiple of 4, got {C_} (use form='composed')")
+    if form == "composed":
+        return _res_block_composed(x, w1, w2, float(res_scale))
+    return _ResBlock.apply(x, w1, w2, float(res_scale))
+
+
+# the form `form=None` runs: decided by tools/lab/edsr_step_time.py (profiles/edsr_step_time.md).  The fused form LOST that measurement --
+# the activation-backward epilogue costs the data-gradient convolution more than the tpgsr_act_bwd pass it replaces, and the ReLU pass the
+# forward saves is within the noise -- so it stays behind form="fused" and the default is the composed form.
+RES_DEFAULT_FORM = "composed"
+
+
+# ---- direct 3x3 convolution to <= 4 channels (EDSR's conv_output, model/edsr.py:57) ---------------------------------------------------
+class _Conv2dNarrow(torch.autograd.Function):
+    """3x3 pad-1 bias-free convolution to 1 .. 4 output channels on the direct kernels (csrc/conv_narrow.hip): the weight is read as
+    PyTorch stores it (nothing is packed), plain fp32 arithmetic under every policy.  The weight gradient's partial sums are finished by
+    tpgsr_reduce_partials on the side stream (into the sink in a recorded plan)."""
+
+    @staticmethod
+    def forward(ctx, x, w):
+        _chk(x, w)
+        x, w = _c(x), _c(w)
+        N, H, W, Cin = x.shape
+        Cout = w.shape[0]
+        y = _new(x, N, H, W, Cout)
+        K.conv3x3_narrow_fwd(x, w, N, H, W, Cin, Cout, y)
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        N, H, W, Cin = x.shape
+        Cout = w.shape[0]
+        dy = _c(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            K.conv3x3_narrow_bwd_data(dy, w, N, H, W, Cin, Cout, dx)
+        if ctx.needs_input_grad[1]:
+            nblk = K.narrow_wgrad_blocks(N, H, W)
+            E = Cout * Cin * 9
+            part = _new(x, nblk, E)
+            sw = _sink(w)
+            with K.side():
+                K.conv3x3_narrow_bwd_weight(x, dy, N, H, W, Cin, Cout, part, nblk)
+                if sw is not None:
+                    K.reduce_partials(part, nblk, E, sw, accumulate=True)
+                else:
+                    dw = torch.empty_like(w)
+                    K.reduce_partials(part, nblk, E, dw, accumulate=False)
+        return dx, dw
+
+
+NARROW_FORMS = ("narrow", "matrix")
+
+
+def conv2d_narrow(x, w, form: Optional[str] = None):
+    """nn.Conv2d(Cin, Cout <= 4, 3, padding=1, bias=False) on an NHWC map.  form "narrow": the direct kernels (Cin a multiple of 4 up to
+    256); "matrix": conv2d(x, w, None, 1), the matrix-core route with Cout padded to a tile; None: NARROW_DEFAULT_FORM."""
+    if form is not None and form not in NARROW_FORMS:
+        raise ValueError(f"conv2d_narrow: form={form!r}, expected one of {NARROW_FORMS} or None")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not 1 <= w.shape[0] <= K.NARROW_MAX_COUT:
+        raise ValueError(f"conv2d_narrow: a [Cout <= {K.NARROW_MAX_COUT}][Cin][3][3] weight, got {tuple(w.shape)}")
+    Cin = w.shape[1]
+    if x.dim() != 4 or x.shape[-1] != Cin:
+        raise ValueError(f"conv2d_narrow: input {tuple(x.shape)} is not (N, H, W, {Cin})")
+    if form is None:
+        form = NARROW_DEFAULT_FORM
+    if form == "matrix":
+        return conv2d(x, w, None, 1)
+    if Cin % 4 or not 4 <= Cin <= K.NARROW_MAX_CIN:
+        raise ValueError(f"conv2d_narrow: the direct kernels take an input channel count that is a multiple of 4 up to {K.NARROW_MAX_CIN}, "
+                         f"got {Cin} (use form='matrix')")
+    return _Conv2dNarrow.apply(x, w)
+
+
+# the form `form=None` runs: decided by tools/lab/edsr_step_time.py (profiles/edsr_step_time.md)
+NARROW_DEFAULT_FORM = "narrow"
+
+
 # ---- pooling / resampling -------------------------------------------------------------------------------------------------
 class _MaxPool(torch.autograd.Function):
     @staticmethod

@@ -45,7 +45,7 @@ CHARBONNIER_EPS = 1e-6      # L1_Charbonnier_loss.eps (model/lapsrn.py:131)
 class ImageCriterion:
     """the image criterion of a train step (interfaces/base.py:332-368) on its kernels: "image_loss" = ImageLoss(gradient, loss_weight) of
     tsrn / tsrn_tl_cascade; "mse" = nn.MSELoss() of srres / vdsr / srresnet_tl / srcnn_tl / vdsr_tl (the image-loss kernels with the
-    gradient term off and w0 = 1); "l1" = nn.L1Loss() of rdn / rdn_tl / esrgan (tpgsr_l1_loss_fwd / _bwd); "l1_charbonnier" =
+    gradient term off and w0 = 1); "l1" = nn.L1Loss() of rdn / rdn_tl / esrgan / edsr (tpgsr_l1_loss_fwd / _bwd); "l1_charbonnier" =
     lapsrn.L1_Charbonnier_loss() of lapsrn (interfaces/base.py:351-353; tpgsr_charbonnier_loss_fwd / _bwd): a SUM over the elements, so
     `.mean()` of the scalar changes nothing and the step's loss is 100 times that sum.  `who` prefixes the refusal of an unknown name."""
 
@@ -90,7 +90,7 @@ def _channel_prefix(src, dst):
 
 def _sr_scale(who, modules) -> int:
     """SR grid / LR grid of a step's SR network(s) (`scale` of their engines: 2 ** up-sampling stages for TSRN / TSRN_TL, 2 for the
-    operator-level backbones but LapSRN and RRDBNet, whose engines carry the module's factor); every stage of a cascade compares with the same HR batch, so they must agree"""
+    operator-level backbones but LapSRN, RRDBNet and EDSR, whose engines carry the module's factor); every stage of a cascade compares with the same HR batch, so they must agree"""
     scales = sorted({int(m._engine().scale) for m in modules})
     if len(scales) != 1:
         raise ValueError(f"{who}: the SR networks of one cascade disagree on scale_factor ({scales})")
@@ -184,7 +184,7 @@ class _TrainStep:
         all-reduce, which stays an ordinary stream-ordered call between them) for world_size > 1.
         `replay(lr, hr)` copies new data into the static buffers and launches the graph(s)."""
         self._lr, self._hr = lr_img.clone(), hr_img.clone()
-        s = torch.cuda.Stream()
+        s = K.fresh_stream()                 # (never the side / aux stream the plans of the step replay on)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
@@ -231,6 +231,7 @@ class TSRNTrainStep(_TrainStep):
         SRTrainStep(vdsr.VDSR(), image_crit="mse", channels=3)
         SRTrainStep(lapsrn.LapSRN(scale_factor=4), image_crit="l1_charbonnier", channels=3)      # --arch lapsrn, no --mask
         SRTrainStep(esrgan.RRDBNet(scale_factor=4), image_crit="l1", channels=3)                 # --arch esrgan, no --mask
+        SRTrainStep(edsr.EDSR(scale_factor=4), image_crit="l1", channels=3)                      # --arch edsr, no --mask
     image_crit: the criterion interfaces/base.py:332-347 pairs with the architecture (`ImageCriterion` above).  channels: the reference's
     channel_num -- the step feeds lr[:, :channels] and compares with hr[:, :channels] (:410-416); the prefix is gathered by a kernel
     launch (tpgsr_copy_strided), so capture() / replay() work on it."""
@@ -670,7 +671,7 @@ class TextSREvaluator:
                  channels: Optional[int] = None):
         self.sr = list(sr_models) if isinstance(sr_models, (list, tuple)) else [sr_models]
         # tpg_models=None: the prior-free pass (interfaces/super_resolution.py:770-793) -- sr = sr_models[0](lr[:, :channels]) for a module
-        # with an engine (tsrn.TSRN, srresnet.SRResNet, rdn.RDN, vdsr.VDSR, lapsrn.LapSRN, esrgan.RRDBNet) or a model.bicubic.BICUBIC; no text-prior generator runs
+        # with an engine (tsrn.TSRN, srresnet.SRResNet, rdn.RDN, vdsr.VDSR, lapsrn.LapSRN, esrgan.RRDBNet, edsr.EDSR) or a model.bicubic.BICUBIC; no text-prior generator runs
         self.plain = tpg_models is None
         self.channels = None if channels is None else int(channels)
         if self.plain:

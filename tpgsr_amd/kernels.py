@@ -268,6 +268,22 @@ def aux_stream(device=None) -> "torch.cuda.Stream":
     return st
 
 
+def fresh_stream(device=None) -> "torch.cuda.Stream":
+    """A torch stream that is neither the side nor the aux stream of its device.  torch hands its streams out of a fixed pool per device,
+    round-robin, so the k-th `torch.cuda.Stream()` of a process can BE the cached side stream: a plan replayed on it has no distinct stream
+    for its weight-gradient launches and tpgsr_plan_run refuses it.  Whoever makes a stream to run train steps on (the warm-up of
+    `capture()`) asks here."""
+    if DRYRUN:
+        return _DummyStream()
+    idx = torch.cuda.current_device() if device is None else torch.device(device).index
+    taken = {st.cuda_stream for st in (_SIDE.get(idx), _AUX.get(idx)) if st is not None}
+    for _ in range(64):
+        st = torch.cuda.Stream(device=idx)
+        if st.cuda_stream not in taken:
+            return st
+    raise RuntimeError("no torch stream apart from the side and aux streams")
+
+
 class Plan:
     """A recorded, replayable list of kernel launches (static pointers + geometry).  Built once per shape by running
     the wrappers below under ``with recording(plan)``; ``run()`` replays it on the current stream with no Python
@@ -1469,6 +1485,52 @@ def tconv4s2_small_bwd_weight(x, dy, N, H, W, Cin, Cout, partial, nblk):
     if not 1 <= nblk <= 65536 or partial.numel() < nblk * Cin * Cout * 16:
         raise ValueError(f"tconv4s2_small_bwd_weight: partial holds {partial.numel()} floats, {nblk} workgroups write {nblk * Cin * Cout * 16}")
     _launch("tpgsr_tconv4s2_small_bwd_weight", _p(x), _p(dy), N, H, W, Cin, Cout, _p(partial), nblk)
+
+
+# ---- direct 3x3 convolution to <= 4 output channels (csrc/conv_narrow.hip) --------------------------------------------
+NARROW_MAX_COUT, NARROW_MAX_CIN = 4, 256
+# the kernels' constants (kRun, kWaves, kGridCap): a wave walks a run of <= NARROW_RUN pixels of one row, a workgroup works on NARROW_WAVES
+# runs at a time and the grid stops at NARROW_GRID_CAP workgroups (grid-stride behind that)
+NARROW_RUN, NARROW_WAVES, NARROW_GRID_CAP = 32, 4, 2048
+NARROW_WGRAD_BLOCKS = 512       # rows of the weight gradient's partial sums at most (one single-wave workgroup each)
+
+
+def narrow_runs(N, H, W) -> int:
+    return N * H * ((W + NARROW_RUN - 1) // NARROW_RUN)
+
+
+def narrow_wgrad_blocks(N, H, W) -> int:
+    return max(1, min(NARROW_WGRAD_BLOCKS, narrow_runs(N, H, W)))
+
+
+def _narrow_check(who, N, H, W, Cin, Cout, x, y, w=None):
+    """the refusals of the C launch functions, made before anything is launched (or recorded)"""
+    if not 1 <= Cout <= NARROW_MAX_COUT:
+        raise ValueError(f"{who}: the direct kernels take 1 to {NARROW_MAX_COUT} output channels, got {Cout}")
+    if Cin % 4 or not 4 <= Cin <= NARROW_MAX_CIN:
+        raise ValueError(f"{who}: the direct kernels take an input channel count that is a multiple of 4 up to {NARROW_MAX_CIN}, got {Cin}")
+    if min(N, H, W) < 1 or N * H * W >= 1 << 27:
+        raise ValueError(f"{who}: needs 1 <= N H W < 2^27 pixels, got {N} x {H} x {W}")
+    if x.numel() != N * H * W * Cin or y.numel() != N * H * W * Cout or (w is not None and w.numel() != Cout * Cin * 9):
+        raise ValueError(f"{who}: tensor sizes do not match N {N}, H {H}, W {W}, Cin {Cin}, Cout {Cout}")
+
+
+def conv3x3_narrow_fwd(x, w, N, H, W, Cin, Cout, y):
+    _narrow_check("conv3x3_narrow_fwd", N, H, W, Cin, Cout, x, y, w)
+    _launch("tpgsr_conv3x3_narrow_fwd", _p(x), _p(w), N, H, W, Cin, Cout, _p(y))
+
+
+def conv3x3_narrow_bwd_data(dy, w, N, H, W, Cin, Cout, dx):
+    _narrow_check("conv3x3_narrow_bwd_data", N, H, W, Cin, Cout, dx, dy, w)
+    _launch("tpgsr_conv3x3_narrow_bwd_data", _p(dy), _p(w), N, H, W, Cin, Cout, _p(dx))
+
+
+def conv3x3_narrow_bwd_weight(x, dy, N, H, W, Cin, Cout, partial, nblk):
+    """partial [nblk][Cout Cin 9]: reduce_partials(partial, nblk, Cout * Cin * 9, dw, accumulate) finishes it"""
+    _narrow_check("conv3x3_narrow_bwd_weight", N, H, W, Cin, Cout, x, dy)
+    if not 1 <= nblk <= 65536 or partial.numel() < nblk * Cout * Cin * 9:
+        raise ValueError(f"conv3x3_narrow_bwd_weight: partial holds {partial.numel()} floats, {nblk} workgroups write {nblk * Cout * Cin * 9}")
+    _launch("tpgsr_conv3x3_narrow_bwd_weight", _p(x), _p(dy), N, H, W, Cin, Cout, _p(partial), nblk)
 
 
 def hreduce(inp, N, H, W, C_, scale, out):

@@ -22,7 +22,11 @@ class FusedAdam:
         self.state = {}
         self.pool = pool          # engine.ArenaPool: all gradient arenas are slices of one buffer (one memset)
         for m in self.modules:
-            frozen = [n for n, p in m.named_parameters() if not p.requires_grad]
+            # A module may declare frozen parameters safe (class attribute FROZEN_BY_ENGINE, a tuple of names: model/edsr.py): its engine never
+            # writes their slices of the gradient arena, so g = m = v = 0 there, Adam's update is lr * 0 / (0 + eps) = 0 exactly and they add 0
+            # to the clip norm -- what torch.optim.Adam + clip_grad_norm_ do for parameters whose .grad is None.
+            declared = set(getattr(type(m), "FROZEN_BY_ENGINE", ()))
+            frozen = [n for n, p in m.named_parameters() if not p.requires_grad and n not in declared]
             if frozen:
                 # the fused step walks the whole flat arena; torch.optim.Adam would skip these tensors
                 raise NotImplementedError(
