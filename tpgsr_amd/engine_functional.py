@@ -165,8 +165,11 @@ class FunctionalEngine:
 
     def _replay_backward(self, N, dout, slot) -> dict:
         """-> the slot's plan dictionary, its backward plan replayed on `dout`"""
+        n = self._saved[slot][0] if slot in self._saved else N
+        if n != N:      # (the slot's activations stay: the backward pass of the forward that owns them still runs)
+            raise RuntimeError(f"{type(self.module).__name__}: backward for a batch of {N} in slot {slot}, whose activations were overwritten "
+                               f"by a later training-mode forward of {n} in the same slot")
         n, pl = self._pop_saved(slot)
-        assert n == N
         self.arena.attach_grads()                       # (same addresses as at trace time: the arena does not move)
         K.copy(dout.contiguous(), pl[self.DOUT], pl[self.DOUT].numel())
         pl["bwd"].run()

@@ -140,6 +140,9 @@ class _TrainStep:
         self.opt = FusedAdam(mods, lr=lr, betas=betas, clip_modules=sr_modules, max_norm=max_norm, pool=self.pool)
         self.pg, self.world = process_group, world_size
         self._graph = self._graph_b = None
+        # static buffers of a step, one set per (device, batch shape): a captured graph holds the addresses of the set it was captured on, so a
+        # step at another shape (the ragged last batch) must not release it.  `_static` is the set of the shape served last.
+        self._statics = {}
         self._static = None
         self._exch = None
 
@@ -193,6 +196,10 @@ class _TrainStep:
         torch.cuda.synchronize()
         ga = torch.cuda.CUDAGraph()
         self._overlap_exchange = False       # the all-reduce stays between the two graphs ...
+        # BatchNorm's num_batches_tracked is kept lazily on the host (engine `_pending_batches`, one per training-mode forward): the capture
+        # executes nothing, so what its forwards counted is taken back, and every replay() counts it instead
+        engines = [m._engine() for m in self.pool.modules]
+        before = [e._pending_batches for e in engines]
         try:
             with torch.cuda.graph(ga), K.policy(self.precision):
                 self._graph_loss = self._phase_a(self._lr, self._hr)
@@ -200,6 +207,12 @@ class _TrainStep:
                     self._phase_b()
         finally:
             self._overlap_exchange = True    # ... and eager step() calls after a capture overlap it with the backward pass again
+        # what the captured step leaves in `last_sr` (and `last_p`): graph memory a replay rewrites -- replay() points the attributes back at
+        # it after an eager step() in between set them to that step's tensors
+        self._graph_last = {k: getattr(self, k) for k in ("last_sr", "last_p") if hasattr(self, k)}
+        self._graph_batches = [(e, e._pending_batches - b) for e, b in zip(engines, before)]
+        for e, b in zip(engines, before):
+            e._pending_batches = b
         self._graph, self._graph_b = ga, None
         if self.world > 1:
             gb = torch.cuda.CUDAGraph()
@@ -220,6 +233,9 @@ class _TrainStep:
         # the captured Adam rewrote the pooled arena behind every version counter: eval-mode forwards after this must re-pack
         for m in self.pool.modules:
             m._engine().invalidate_packed()
+        for e, n in self._graph_batches:
+            e._pending_batches += n
+        self.__dict__.update(self._graph_last)
         return self._graph_loss
 
 
@@ -250,7 +266,10 @@ class TSRNTrainStep(_TrainStep):
     # -- one step as plain launches ---------------------------------------------------------------------------
     def _buffers(self, lr_img):
         dev = lr_img.device
-        if self._static is None or self._static["dev"] != dev or self._static["shape"] != tuple(lr_img.shape):
+        key = (dev, tuple(lr_img.shape))
+        if self._static is None or self._static["dev"] != dev or self._static["shape"] != key[1]:
+            self._static = self._statics.get(key)
+        if self._static is None:
             N, C, H, W = lr_img.shape
             if self.channels is not None and self.channels > C:
                 raise ValueError(f"TSRNTrainStep: channels={self.channels} of a batch with {C} planes")
@@ -262,6 +281,7 @@ class TSRNTrainStep(_TrainStep):
                                 inv_world=torch.full((1,), 1.0 / self.world, device=dev))
             if Cs != C:      # the channel prefixes the network and the criterion see
                 self._static.update(lr_c=torch.empty(N, Cs, H, W, device=dev), hr_c=torch.empty(N, Cs, s * H, s * W, device=dev))
+            self._statics[key] = self._static
         return self._static
 
     def _phase_a(self, lr_img, hr_img):
@@ -386,11 +406,14 @@ class TPGSRTrainStep(_TrainStep):
 
     def _buffers(self, lr_img):
         dev, N = lr_img.device, lr_img.shape[0]
-        if self._static is None or self._static["key"] != (dev, tuple(lr_img.shape)):
+        key = (dev, tuple(lr_img.shape))
+        if self._static is None or self._static["key"] != key:
+            self._static = self._statics.get(key)
+        if self._static is None:
             _, C, H, W = lr_img.shape
             S = self.stu_iter
             s = _sr_scale("TPGSRTrainStep", self.sr)
-            st = dict(key=(dev, tuple(lr_img.shape)), scale=s, q=torch.empty(N, 26, 37, device=dev),
+            st = dict(key=key, scale=s, q=torch.empty(N, 26, 37, device=dev),
                       gray_hr=torch.empty(N, 1, 32, 100, device=dev), loss=torch.zeros((), device=dev),
                       dloss=torch.full((1,), 100.0, device=dev), inv_world=torch.full((1,), 1.0 / self.world, device=dev),
                       part_img=[torch.empty(_NBLK_IMG, 2, device=dev) for _ in range(S)],
@@ -408,7 +431,7 @@ class TPGSRTrainStep(_TrainStep):
                 cc = min(C, 3)
                 st.update(ssim_win=create_window(11, 1)[0, 0].contiguous().to(dev), ssim_part=torch.empty(256, dtype=torch.float64, device=dev),
                           ssim_out=torch.empty(1, device=dev), ssim_gm=torch.empty(3 * N * cc * s * s * H * W, device=dev))
-            self._static = st
+            self._static = self._statics[key] = st
         return self._static
 
     def _labels(self, labels, N, dev):
