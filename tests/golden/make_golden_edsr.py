@@ -9,7 +9,7 @@ make_golden_next.py, seeds in `SEEDS` -- the four frozen MeanShift tensors inclu
 `synthetic_batch(n, seed, scale=s)`: the tests rebuild both, only results are stored (no 160 MB of weights).  Every stored forward result
 is first compared with this file's own float64 restatement of the network (`edsr_forward`, plain torch.nn.functional -- the tests import it
 as their float64 reference where no fixture is stored), and the reference's float32 run has to stay within a QUARTER of every bound
-tests/test_edsr_gpu.py applies, measured against float64 (`BOUNDS`); a seed set that does not is replaced by the next one (every seed moved
+tests/test_edsr_gpu.py applies, measured against float64 (`BOUNDS` and the fixture skeletons of golden_plain_arch.py); a seed set that does not is replaced by the next one (every seed moved
 up by 1000) and the count of sets tried is printed.  SR images are stored for the first `N_STORE[scale]` samples of a batch.
 
     python tests/golden/make_golden_edsr.py     # rewrites tests/golden/edsr_x{2,4}.npz, train_edsr_x{2,4}.npz, edsr_layouts.json"""
@@ -17,7 +17,6 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -26,9 +25,8 @@ ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
-from make_golden_lapsrn import to64  # noqa: E402,F401  (re-exported for the tests)
-from make_golden_next import generic_recipe, grad_summary  # noqa: E402
-from make_golden_rrdb import ssim64, ssim_window  # noqa: E402,F401
+from golden_plain_arch import (BOUNDS, OverMargin, Recipe, eval_fixture, model_fixture, save_pair, ssim64, ssim_window, to64,  # noqa: E402,F401
+                               train_fixture)      # (ssim64 -- RRDBNet's, over the float32-built taps -- and to64 are re-exported for the tests)
 
 SCALES = (2, 4)
 DEPTHS = (32, 2)
@@ -41,8 +39,6 @@ N_SMALL, SMALL_HW = 1, (12, 40)
 N_STORE = {2: 2, 4: 1}                                            # samples of a 16x64 batch whose SR image is stored
 RES_SCALE = 0.1
 FROZEN = ("sub_mean.weight", "sub_mean.bias", "add_mean.weight", "add_mean.bias")
-# the bounds of tests/test_edsr_gpu.py (those of tests/test_rrdb_gpu.py for the same quantities)
-BOUNDS = dict(fwd=1e-4, grad=5e-3, head=0.1, loss=3e-4, gnorm=3e-3, loss2=2e-2, dpsnr=1e-5, dssim=1e-7)
 # the evaluator batch (N = 6, depth EVAL_NB): weight seeds of the network (per scale) and of the CRNN recogniser; the data seed is CHOSEN below
 EVAL_N, EVAL_NB, EVAL_SEEDS = 6, 2, {2: 625, 4: 626, "rec": 60}
 EVAL_DATA_SEEDS = range(400, 464)
@@ -72,164 +68,8 @@ def build_reference(R, scale, nb):
     return net
 
 
-def _rel(a, b):
-    return float((a.double() - b.double()).abs().max()) / max(1.0, float(b.double().abs().max()))
-
-
-class OverMargin(AssertionError):
-    pass
-
-
-def _quarter(err, bound, what):
-    if not err <= 0.25 * bound:
-        raise OverMargin(f"{what}: the reference's float32 run is {err:.2e} from float64, more than a quarter of the bound {bound:.0e}")
-    return err
-
-
-def _grad_errors(net32, p64):
-    """the per-parameter rule of check_param_grads (tests/test_tl_cascade_gpu.py), float32 reference against float64; frozen tensors have
-    no gradient on either side"""
-    n64 = {k: float(v.grad.norm()) for k, v in p64.items() if v.grad is not None}
-    gmax = max(n64.values())
-    en = eh = 0.0
-    worst = None
-    for k, q in net32.named_parameters():
-        if k in FROZEN:
-            assert q.grad is None and p64[k].grad is None, k
-            continue
-        g32, g64 = q.grad.double(), p64[k].grad
-        e = abs(float(g32.norm()) - n64[k]) / max(n64[k], 1e-3 * gmax)
-        if e > en:
-            en, worst = e, k
-        sc = max(n64[k], 1e-3 * gmax) / np.sqrt(g64.numel())
-        eh = max(eh, float((g32.reshape(-1)[:8] - g64.reshape(-1)[:8]).abs().max()) / sc)
-    print(f"  worst parameter-gradient norm: {worst} {en:.2e} (|g| {n64[worst]:.3e}, largest {gmax:.3e})")
-    return en, eh
-
-
-def _p64(sd):
-    p = to64(sd)
-    for k, v in p.items():
-        if k not in FROZEN:
-            v.requires_grad_(True)
-    return p
-
-
-def model_fixture(nb, s, seeds, R, O):
-    dseed, wseed, gseed, sseed = seeds
-    n = N[nb]
-    lr = O.synthetic_batch(n, dseed, scale=s)[0][:, :CHANNELS].contiguous()
-    lr_s = O.synthetic_batch(N_SMALL, sseed, lr_hw=SMALL_HW, scale=s)[0][:, :CHANNELS].contiguous()
-    ref = build_reference(R, s, nb)
-    sd = generic_recipe(ref.state_dict(), wseed)
-    ref.load_state_dict(sd, strict=True)
-    assert [k for k, q in ref.named_parameters() if not q.requires_grad] == list(FROZEN)
-    ref.eval()
-    with torch.no_grad():
-        ys = ref(lr_s)
-        _quarter(_rel(ys, edsr_forward(to64(sd), lr_s.double(), s, nb)), BOUNDS["fwd"], f"nb {nb} x{s} eval 12x40")
-    ref.train()
-    y = ref(lr)
-    gy = torch.randn(y.shape, generator=torch.Generator().manual_seed(gseed))
-    (y * gy).sum().backward()
-    p64 = _p64(sd)
-    y64 = edsr_forward(p64, lr.double(), s, nb)
-    e = _quarter(_rel(y.detach(), y64.detach()), BOUNDS["fwd"], f"nb {nb} x{s} train")
-    (y64 * gy.double()).sum().backward()
-    en, eh = _grad_errors(ref, p64)
-    _quarter(en, BOUNDS["grad"], f"nb {nb} x{s} parameter-gradient norms")
-    _quarter(eh, BOUNDS["head"], f"nb {nb} x{s} parameter-gradient heads")
-    names, norms, heads = grad_summary(ref)
-    print(f"nb {nb} x{s}: y {tuple(y.shape)}, {len(names)} parameters, |y| max {float(y.abs().max()):.3f}; float32 against float64: forward "
-          f"{e:.2e}, gradient norms {en:.2e}, heads {eh:.2e}")
-    pre = f"nb{nb}_"
-    return {pre + "y": y.detach().numpy()[:N_STORE[s]], pre + "y_small": ys.numpy(), pre + "grad_names": names, pre + "grad_norms": norms,
-            pre + "grad_heads": heads, pre + "seeds": np.array([dseed, wseed, gseed, sseed])}
-
-
-def train_fixture(nb, s, seeds, R, O):
-    """two steps of the reference loop body (:409-424): nn.L1Loss()(model(lr[:, :3]), hr[:, :3]).mean() * 100, clip 0.25, Adam(lr 1e-3,
-    betas (0.5, 0.999)) over model.parameters() -- and the same two steps in float64 over the restatement"""
-    dseed, wseed, _, _ = seeds
-    lr, hr = O.synthetic_batch(N[nb], dseed, scale=s)
-    net = build_reference(R, s, nb)
-    sd = generic_recipe(net.state_dict(), wseed)
-    net.load_state_dict(sd)
-    net.train()
-    opt = torch.optim.Adam(net.parameters(), lr=1e-3, betas=(0.5, 0.999))
-    crit = torch.nn.L1Loss()
-    p64 = _p64(sd)
-    train64 = [v for k, v in p64.items() if k not in FROZEN]
-    opt64 = torch.optim.Adam(train64, lr=1e-3, betas=(0.5, 0.999))
-    loss_l, gn_l = [], []
-    for step in range(2):
-        sr = net(lr[:, :CHANNELS, ...])
-        loss = crit(sr, hr[:, :CHANNELS, ...]).mean() * 100
-        opt.zero_grad()
-        loss.backward()
-        if step == 0:
-            gs = grad_summary(net)
-            sr0 = sr.detach().numpy()[:N_STORE[s]]
-        gn = torch.nn.utils.clip_grad_norm_(net.parameters(), 0.25)
-        opt.step()
-        sr64 = edsr_forward(p64, lr[:, :CHANNELS].double(), s, nb)
-        loss64 = (sr64 - hr[:, :CHANNELS].double()).abs().mean() * 100
-        opt64.zero_grad()
-        loss64.backward()
-        gn64 = torch.nn.utils.clip_grad_norm_(train64, 0.25)
-        opt64.step()
-        _quarter(abs(loss.item() - loss64.item()) / loss64.item(), BOUNDS["loss" if step == 0 else "loss2"], f"nb {nb} x{s} loss, step {step}")
-        if step == 0:
-            _quarter(abs(float(gn) - float(gn64)) / float(gn64), BOUNDS["gnorm"], f"nb {nb} x{s} clip norm")
-            _quarter(_rel(sr.detach(), sr64.detach()), BOUNDS["fwd"], f"nb {nb} x{s} sr_step0")
-        loss_l.append(loss.item())
-        gn_l.append(float(gn))
-        print(f"  nb {nb} x{s} step {step}: loss {loss.item():.6f} (float64 {loss64.item():.6f})  clip norm {float(gn):.5f} (float64 {float(gn64):.5f})")
-    for k in FROZEN:                                               # torch.optim.Adam skips parameters without a gradient
-        assert torch.equal(net.state_dict()[k], sd[k]), k
-    pre = f"nb{nb}_"
-    return {pre + "loss": np.array(loss_l), pre + "gnorm": np.array(gn_l), pre + "sr_step0": sr0, pre + "sr_grad_names": gs[0],
-            pre + "sr_grad_norms": gs[1], pre + "sr_grad_heads": gs[2], pre + "seeds": np.array([dseed, wseed])}
-
-
-def eval_fixture(s, R, O):
-    """the evaluator batch of a factor: the first data seed at which the recogniser's float32 and float64 arg-max agree at every time step
-    for LR, HR and the SR image; the expected strings = the oracle's CRNN forward + greedy decode on the reference SR image"""
-    sd_r = O.recipe_state_dict(O.crnn_spec(), EVAL_SEEDS["rec"])
-    r32, r64 = O.as_params(sd_r, False), O.as_params(to64(sd_r), False)
-    ref = build_reference(R, s, EVAL_NB)
-    sd = generic_recipe(ref.state_dict(), EVAL_SEEDS[s])
-    ref.load_state_dict(sd, strict=True)
-    ref.eval()
-
-    def logits(img, p):
-        return O.crnn_forward(p, O.parse_crnn_data(img[:, :3]), training=False)
-
-    with torch.no_grad():
-        for tried, seed in enumerate(EVAL_DATA_SEEDS, 1):
-            lr, hr = O.synthetic_batch(EVAL_N, seed, scale=s)
-            sr = ref(lr[:, :CHANNELS])
-            sr64 = edsr_forward(to64(sd), lr[:, :CHANNELS].double(), s, EVAL_NB)
-            _quarter(_rel(sr, sr64), BOUNDS["fwd"], f"evaluator x{s} SR")
-            hr64 = hr[:, :CHANNELS].double()
-            dp = abs(float(O.calculate_psnr(sr.double(), hr64)) - float(O.calculate_psnr(sr64, hr64)))
-            ds = abs(float(ssim64(sr.double(), hr64)) - float(ssim64(sr64, hr64)))
-            if dp > 0.25 * BOUNDS["dpsnr"] or ds > 0.25 * BOUNDS["dssim"]:
-                print(f"  evaluator batch x{s} seed {seed}: the float32 reference image moves PSNR by {dp:.2e} dB, SSIM by {ds:.2e}, next seed")
-                continue
-            res, ok = {}, True
-            for k, img in (("lr", lr), ("hr", hr), ("sr", sr)):
-                l32, l64 = logits(img, r32), logits(img.double(), r64)
-                if not torch.equal(l32.argmax(-1), l64.argmax(-1)):
-                    ok = False
-                    break
-                res[k] = O.get_string_crnn(l32)
-            if not ok:
-                print(f"  evaluator batch x{s} seed {seed}: float32 / float64 arg-max differ, next seed")
-                continue
-            print(f"evaluator batch x{s}: data seed {seed} ({tried} tried; float32 image moves PSNR by {dp:.2e} dB, SSIM by {ds:.2e})", res)
-            return dict(eval_seed=np.array(seed), eval_lr=np.array(res["lr"]), eval_hr=np.array(res["hr"]), eval_sr=np.array(res["sr"]))
-    raise RuntimeError("no evaluator batch with agreeing float32 / float64 arg-max among the candidate seeds")
+RECIPE = Recipe(build=build_reference, forward=edsr_forward, frozen=FROZEN, channels=CHANNELS, n=N, n_store=N_STORE, n_small=N_SMALL,
+                small_hw=SMALL_HW, eval_n=EVAL_N, eval_nb=EVAL_NB, eval_seeds=EVAL_SEEDS, eval_data_seeds=EVAL_DATA_SEEDS)
 
 
 def fixtures_with_margin(nb, s, R, O, max_sets=8):
@@ -237,7 +77,7 @@ def fixtures_with_margin(nb, s, R, O, max_sets=8):
     for tried in range(max_sets):
         seeds = tuple(v + 1000 * tried for v in SEEDS[(nb, s)])
         try:
-            m, t = model_fixture(nb, s, seeds, R, O), train_fixture(nb, s, seeds, R, O)
+            m, t = model_fixture(RECIPE, nb, s, seeds, R, O), train_fixture(RECIPE, nb, s, seeds, R, O)
         except OverMargin as e:
             print(f"  nb {nb} x{s} seed set {seeds}: {e}; next set")
             continue
@@ -272,11 +112,8 @@ def main():
                 moved[(nb, s)] = seeds
             model.update(m)
             train.update(t)
-        model.update(eval_fixture(s, R, O))
-        np.savez_compressed(os.path.join(HERE, f"edsr_x{s}.npz"), **model)
-        np.savez_compressed(os.path.join(HERE, f"train_edsr_x{s}.npz"), **train)
-        for f in (f"edsr_x{s}.npz", f"train_edsr_x{s}.npz"):
-            assert os.path.getsize(os.path.join(HERE, f)) < 700 * 1024, f
+        model.update(eval_fixture(RECIPE, s, R, O))
+        save_pair(HERE, "edsr", s, model, train)
     json.dump(layouts, open(os.path.join(HERE, "edsr_layouts.json"), "w"), indent=0)
     assert not moved, f"update SEEDS to {moved} and run again: the tests rebuild weights and inputs from SEEDS"
     print("edsr_x*.npz, train_edsr_x*.npz, edsr_layouts.json written")

@@ -22,6 +22,8 @@ ROOT = os.path.abspath(os.path.join(HERE, "..", ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
+from golden_plain_arch import Recipe, eval_fixture, save_pair, to64  # noqa: E402
+from golden_plain_arch import ssim64 as _ssim64  # noqa: E402
 from make_golden_next import generic_recipe, grad_summary  # noqa: E402
 
 SCALES = (2, 4)
@@ -57,23 +59,8 @@ def charbonnier(sr, hr):
 
 
 def ssim64(img1, img2, window_size=11):
-    """utils/ssim_psnr.py SSIM(window_size=11, size_average=True) in the dtype of its inputs (oracle.tpgsr_oracle.ssim keeps a float32 window)"""
-    a, b = img1[:, :3], img2[:, :3]
-    ch = a.shape[1]
-    g = torch.exp(-(torch.arange(window_size, dtype=torch.float64) - window_size // 2) ** 2 / (2 * 1.5 ** 2))
-    g = (g / g.sum()).unsqueeze(1)
-    w = g.mm(g.t()).float().to(a.dtype).expand(ch, 1, window_size, window_size).contiguous()      # (the reference rounds its window to float32)
-    pd = window_size // 2
-    mu1, mu2 = F.conv2d(a, w, padding=pd, groups=ch), F.conv2d(b, w, padding=pd, groups=ch)
-    s11 = F.conv2d(a * a, w, padding=pd, groups=ch) - mu1 * mu1
-    s22 = F.conv2d(b * b, w, padding=pd, groups=ch) - mu2 * mu2
-    s12 = F.conv2d(a * b, w, padding=pd, groups=ch) - mu1 * mu2
-    c1, c2 = 0.01 ** 2, 0.03 ** 2
-    return (((2 * mu1 * mu2 + c1) * (2 * s12 + c2)) / ((mu1 * mu1 + mu2 * mu2 + c1) * (s11 + s22 + c2))).mean()
-
-
-def to64(sd):
-    return {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    """golden_plain_arch.ssim64 over taps built in float64 and rounded to float32 afterwards (oracle.tpgsr_oracle.ssim keeps a float32 window)"""
+    return _ssim64(img1, img2, window_size, taps=torch.float64)
 
 
 def _close(a, b, what, tol=2e-5):
@@ -121,7 +108,7 @@ def model_fixture(s, R, O):
     print(f"x{s}: y {tuple(y.shape)}, {len(names)} parameters, |y| max {float(y.abs().max()):.3f}")
     out = dict(y=y.detach().numpy()[:N_STORE[s]], y_small=ys.numpy(), grad_names=names, grad_norms=norms, grad_heads=heads,
                seeds=np.array([dseed, wseed, gseed, sseed]))
-    out.update(eval_fixture(s, R, O))
+    out.update(eval_fixture(RECIPE, s, R, O))
     return out
 
 
@@ -153,38 +140,11 @@ def train_fixture(s, R, O):
                 seeds=np.array([dseed, wseed]))
 
 
-def eval_fixture(s, R, O):
-    """the evaluator batch of a factor: the first data seed at which the recogniser's float32 and float64 arg-max agree at every time step
-    for LR, HR and the SR image; the expected strings = the oracle's CRNN forward + greedy decode on the reference SR image"""
-    sd_r = O.recipe_state_dict(O.crnn_spec(), EVAL_SEEDS["rec"])
-    r32, r64 = O.as_params(sd_r, False), O.as_params(to64(sd_r), False)
-    ref = R.lapsrn.LapSRN(scale_factor=s, width=128, height=32, STN=False)
-    sd = generic_recipe(ref.state_dict(), EVAL_SEEDS[s])
-    ref.load_state_dict(sd, strict=True)
-    ref.eval()
-
-    def logits(img, p):
-        return O.crnn_forward(p, O.parse_crnn_data(img[:, :3]), training=False)
-
-    with torch.no_grad():
-        for seed in EVAL_DATA_SEEDS:
-            lr, hr = O.synthetic_batch(EVAL_N, seed, scale=s)
-            sr = ref(lr[:, :CHANNELS])
-            sr64 = lapsrn_forward(to64(sd), lr[:, :CHANNELS].double(), s)
-            _close(sr, sr64, f"evaluator x{s} SR")
-            res, ok = {}, True
-            for k, img in (("lr", lr), ("hr", hr), ("sr", sr)):
-                l32, l64 = logits(img, r32), logits(img.double(), r64)
-                if not torch.equal(l32.argmax(-1), l64.argmax(-1)):
-                    ok = False
-                    break
-                res[k] = O.get_string_crnn(l32)
-            if not ok:
-                print(f"  evaluator batch x{s} seed {seed}: float32 / float64 arg-max differ, next seed")
-                continue
-            print(f"evaluator batch x{s}: data seed {seed}", res)
-            return dict(eval_seed=np.array(seed), eval_lr=np.array(res["lr"]), eval_hr=np.array(res["hr"]), eval_sr=np.array(res["sr"]))
-    raise RuntimeError("no evaluator batch with agreeing float32 / float64 arg-max among the candidate seeds")
+# the evaluator batch: golden_plain_arch.eval_fixture under this file's own forward tolerance (_close) and without the metric margin
+RECIPE = Recipe(build=lambda R, s, nb: R.lapsrn.LapSRN(scale_factor=s, width=128, height=32, STN=False),
+                forward=lambda p, x, s, nb: lapsrn_forward(p, x, s), channels=CHANNELS, n={None: N}, n_store=N_STORE, n_small=N_SMALL,
+                small_hw=SMALL_HW, eval_n=EVAL_N, eval_nb=None, eval_seeds=EVAL_SEEDS, eval_data_seeds=EVAL_DATA_SEEDS, fwd_tol=2e-5,
+                metric_margin=False)
 
 
 def main():
@@ -203,8 +163,7 @@ def main():
         layouts[f"x{s}"] = [(k, list(v.shape)) for k, v in net.state_dict().items()]
         tent = torch.tensor([0.25, 0.75, 0.75, 0.25])
         assert all(torch.equal(v, torch.outer(tent, tent).expand_as(v)) for k, v in net.state_dict().items() if k.startswith("convt_I") or k.endswith(".20.weight"))
-        np.savez_compressed(os.path.join(HERE, f"lapsrn_x{s}.npz"), **model_fixture(s, R, O))
-        np.savez_compressed(os.path.join(HERE, f"train_lapsrn_x{s}.npz"), **train_fixture(s, R, O))
+        save_pair(HERE, "lapsrn", s, model_fixture(s, R, O), train_fixture(s, R, O))
     json.dump(layouts, open(os.path.join(HERE, "lapsrn_layouts.json"), "w"), indent=0)
     print("lapsrn_x*.npz, train_lapsrn_x*.npz, lapsrn_layouts.json written")
 

@@ -4,16 +4,13 @@ mode (TPGSR_PLAN_DRYRUN=1, the pattern of tests/test_plain_baselines_cpu.py) thr
 the prior-free evaluator pass; the committed fixtures."""
 import json
 import os
-import re
-import subprocess
 import sys
 
-import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-GOLD = os.path.join(ROOT, "tests", "golden")
+from plain_arch_record import GOLD, ROOT, check_criterion_kernels, check_entry_points, check_evaluator_case, check_fixtures, record
+
 sys.path.insert(0, ROOT)
 sys.path.insert(0, GOLD)
 
@@ -80,15 +77,7 @@ def test_refusals():
 
 
 def test_new_entry_points_are_declared_bound_and_registered():
-    from tpgsr_amd import _lib
-    header = open(os.path.join(ROOT, "include", "tpgsr_hip.h")).read()
-    plan = open(os.path.join(ROOT, "tpgsr_amd", "csrc", "plan.cpp")).read()
-    for sym in NEW_SYMBOLS:
-        assert sym in _lib.EXPORTED_SYMBOLS
-        assert re.search(r"\bint\s+%s\s*\(" % sym, header)
-        assert "TPGSR_REG(%s)" % sym in plan
-        assert hasattr(_lib.load(), sym)
-    assert len(_lib.ABI_STRUCTS) == 13      # scalar parameters only
+    check_entry_points(NEW_SYMBOLS, None, 13)      # (the kernels went into source files the build already listed)
 
 
 def test_form_table_of_the_transposed_convolution():
@@ -98,62 +87,17 @@ def test_form_table_of_the_transposed_convolution():
     assert Fh.tconv_k4s2_form(8, 8) == Fh.tconv_k4s2_form(5, 3) == "dilated"
 
 
-RECORD = r'''
-import json, sys, torch
-sys.path.insert(0, %(root)r)
-from tpgsr_amd import kernels as K
-assert K.DRYRUN
-from tpgsr_amd import functional as Fh
-from tpgsr_amd.engine_functional import PlainSREngine
-from tpgsr_amd.interfaces.super_resolution import SRTrainStep, TextSREvaluator
-from tpgsr_amd.model import lapsrn, srresnet
-from tpgsr_amd.model.crnn import crnn
-
-direct = []
-_launch = K._launch
-def spy(name, *a):
-    if K._REC is None:
-        direct.append(name)
-    return _launch(name, *a)
-K._launch = spy
-
-def err(f):
-    try:
-        f()
-    except Exception as e:
-        return [type(e).__name__, str(e)]
-    return None
-
-out = {}
-torch.manual_seed(0)
+IMPORTS = "from tpgsr_amd.model import lapsrn, srresnet"
+CASES = r'''
 for s in (2, 4):
-    del direct[:]
-    net = lapsrn.LapSRN(scale_factor=s).train()
-    ts = SRTrainStep(net, precision="x3", image_crit="l1_charbonnier", channels=3)
-    loss = ts.step(torch.rand(4, 4, 16, 64), torch.rand(4, 4, 16 * s, 64 * s))
-    eng = net._engine()
-    assert isinstance(eng, PlainSREngine) and eng.record and tuple(loss.shape) == ()
-    (key, pl), = eng._plans.items()
-    for p in (pl["fwd"], pl["bwd"]):
-        p.run()                                   # the native executor checks entry point and argument count of every op
-    a, b = ts.pool.ranges[id(net)]
-    live = [n for n, p in net.named_parameters() if s == 4 or not n.startswith(("convt_I2", "convt_R2", "convt_F2"))]
-    out[str(s)] = dict(key=[str(k) for k in key], fwd=[o[0] for o in pl["fwd"].ops], bwd=[o[0] for o in pl["bwd"].ops], direct=list(direct),
-                       sr=list(ts.last_sr.shape), scale=eng.scale, pooled=bool(eng.arena.external is not None and b - a == eng.arena.numel),
-                       sunk=all(p.grad is not None for p in net.parameters()), n_live=len(live), has_prior=("prior" in pl or "dprior" in pl),
-                       wrong_hr=err(lambda: ts.step(torch.rand(4, 4, 16, 64), torch.rand(4, 4, 8 * s, 32 * s))))
+    out[str(s)] = train_case(lambda: lapsrn.LapSRN(scale_factor=s), s, "l1_charbonnier")
+    out[str(s)]["n_live"] = len([n for n, p in lapsrn.LapSRN(scale_factor=s).named_parameters()
+                                 if s == 4 or not n.startswith(("convt_I2", "convt_R2", "convt_F2"))])
+    out["eval_%d" % s] = eval_case(lambda: lapsrn.LapSRN(scale_factor=s), s)
 out["srres_scale"] = srresnet.SRResNet()._engine().scale
 out["class_scale"] = PlainSREngine.scale
-
-rec = crnn.CRNN(32, 1, 37, 256).eval()
-for s in (2, 4):
-    del direct[:]
-    net = lapsrn.LapSRN(scale_factor=s).eval()
-    ev = TextSREvaluator([net], None, recognizer=rec, channels=3)
-    srs, priors = ev.super_resolve(torch.rand(6, 4, 16, 64))
-    (pl,) = net._engine()._plans.values()
-    out["eval_%%d" %% s] = dict(direct=list(direct), sr=list(srs[0].shape), priors=len(priors), plan=[o[0] for o in pl["fwd"].ops])
-
+'''
+EXTRA = r'''
 # the other forms of the functional op, and its refusals
 x = torch.rand(2, 3, 5, 8).requires_grad_(True)
 w = torch.rand(8, 8, 4, 4).requires_grad_(True)
@@ -164,18 +108,12 @@ out["dilated_8x8"] = dict(direct=list(direct), y=list(y.shape))
 out["bad_form"] = err(lambda: Fh.conv_transpose2d_k4s2(x, w, form="subpixel"))
 out["bad_weight"] = err(lambda: Fh.conv_transpose2d_k4s2(x, torch.rand(8, 8, 3, 3)))
 out["cin5"] = err(lambda: K.tconv4s2_small_fwd(torch.rand(1, 2, 2, 5), torch.rand(5, 3, 4, 4), 1, 2, 2, 5, 3, torch.rand(1, 4, 4, 3)))
-print("RESULT " + json.dumps(out))
 '''
 
 
 @pytest.fixture(scope="module")
 def rec():
-    env = dict(os.environ, TPGSR_PLAN_DRYRUN="1")
-    for k in [k for k in env if k.startswith("TPGSR_") and k != "TPGSR_PLAN_DRYRUN"]:
-        del env[k]
-    r = subprocess.run([sys.executable, "-c", RECORD % dict(root=ROOT)], capture_output=True, text=True, env=env, timeout=550)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    return record(IMPORTS, CASES, EXTRA)
 
 
 @pytest.mark.timeout(600)
@@ -207,11 +145,7 @@ def test_lapsrn_records_forward_and_backward_plans_without_gpu(rec, scale):
 
 
 def test_l1_charbonnier_records_its_kernels(rec):
-    for s in ("2", "4"):
-        d = rec[s]["direct"]
-        assert "tpgsr_charbonnier_loss_fwd" in d and "tpgsr_charbonnier_loss_bwd" in d and "tpgsr_image_loss_finalize" in d
-        assert "tpgsr_image_loss_fwd" not in d and "tpgsr_l1_loss_fwd" not in d and "tpgsr_image_loss_bwd" not in d
-        assert d.count("tpgsr_copy_strided") == 2          # channels=3: the RGB prefixes of LR and HR
+    check_criterion_kernels(rec, ("2", "4"), "l1_charbonnier")
 
 
 def test_engine_scale_is_the_modules_factor(rec):
@@ -225,9 +159,7 @@ def test_engine_scale_is_the_modules_factor(rec):
 def test_evaluator_pass_takes_both_factors(rec):
     for s in (2, 4):
         r = rec[f"eval_{s}"]
-        assert r["sr"] == [6, 3, 16 * s, 64 * s] and r["priors"] == 0
-        # one recorded forward plan behind the channel-prefix copy: no text-prior launch next to it
-        assert r["direct"] == ["tpgsr_copy_strided", "tpgsr_copy", "tpgsr_copy"]
+        check_evaluator_case(r, s)
         assert "tpgsr_dilate2d" not in r["plan"] and r["plan"].count("tpgsr_tconv4s2_expand") == s // 2
 
 
@@ -241,19 +173,5 @@ def test_functional_op_fallback_and_refusals(rec):
 
 @pytest.mark.parametrize("scale", [2, 4])
 def test_fixtures_load_and_are_finite(scale):
-    from make_golden_lapsrn import N_STORE
-    from tpgsr_amd.model import lapsrn
-    g = np.load(os.path.join(GOLD, f"lapsrn_x{scale}.npz"), allow_pickle=False)
-    t = np.load(os.path.join(GOLD, f"train_lapsrn_x{scale}.npz"), allow_pickle=False)
-    for path in (f"lapsrn_x{scale}.npz", f"train_lapsrn_x{scale}.npz"):
-        assert os.path.getsize(os.path.join(GOLD, path)) < 700 * 1024
-    assert g["y"].shape == t["sr_step0"].shape == (N_STORE[scale], 3, 16 * scale, 64 * scale)
-    assert g["y_small"].shape == (2, 3, 12 * scale, 40 * scale)
-    assert t["loss"].shape == (2,) and t["gnorm"].shape == (2,) and (t["loss"] > 0).all() and (t["gnorm"] > 0).all()
-    for k in ("y", "y_small", "grad_norms", "grad_heads"):
-        assert np.isfinite(g[k]).all() and g[k].size, k
-    names = [n for n, _ in lapsrn.LapSRN(scale_factor=scale).named_parameters()]
-    assert [str(n) for n in g["grad_names"]] == names
-    live = np.array([scale == 4 or not n.startswith(("convt_I2", "convt_R2", "convt_F2")) for n in names])
-    assert (g["grad_norms"][live] > 0).all() and (g["grad_norms"][~live] == 0).all()      # x2: the second stage has no gradient
-    assert len(g["eval_sr"]) == len(g["eval_lr"]) == len(g["eval_hr"]) == 6
+    import plain_arch_common as P
+    check_fixtures(P.LAPSRN, scale)

@@ -5,16 +5,13 @@ block and through the prior-free evaluator pass; the committed fixtures."""
 import inspect
 import json
 import os
-import re
-import subprocess
 import sys
 
-import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-GOLD = os.path.join(ROOT, "tests", "golden")
+from plain_arch_record import GOLD, ROOT, check_criterion_kernels, check_entry_points, check_evaluator_case, check_fixtures, record
+
 sys.path.insert(0, ROOT)
 sys.path.insert(0, GOLD)
 
@@ -93,78 +90,25 @@ def test_refusals():
 
 
 def test_new_entry_points_are_declared_bound_and_registered():
-    from tpgsr_amd import _lib
-    from tpgsr_amd.build import SOURCES
-    header = open(os.path.join(ROOT, "include", "tpgsr_hip.h")).read()
-    plan = open(os.path.join(ROOT, "tpgsr_amd", "csrc", "plan.cpp")).read()
-    assert "dense.hip" in SOURCES
-    for sym in NEW_SYMBOLS:
-        assert sym in _lib.EXPORTED_SYMBOLS
-        assert re.search(r"\bint\s+%s\s*\(" % sym, header)
-        assert "TPGSR_REG(%s)" % sym in plan
-        fn = getattr(_lib.load(), sym)
-        assert len(fn.argtypes) <= 24 + 1
-    assert len(_lib.ABI_STRUCTS) == 13      # scalar and pointer parameters only: no new argument block
+    check_entry_points(NEW_SYMBOLS, "dense.hip", 13)
 
 
-RECORD = r'''
-import json, sys, torch
-sys.path.insert(0, %(root)r)
-sys.path.insert(0, %(tests)r)
-from tpgsr_amd import kernels as K
-assert K.DRYRUN
-from tpgsr_amd import functional as Fh
-from tpgsr_amd.engine_functional import PlainSREngine
-from tpgsr_amd.interfaces.super_resolution import SRTrainStep, TextSREvaluator
-from tpgsr_amd.model import esrgan
-from tpgsr_amd.model.crnn import crnn
-from plan_signature import signature
+IMPORTS = "from tpgsr_amd.model import esrgan"
+CASES = r'''
+def rrdb_net(s, form=None):
+    net = esrgan.RRDBNet(scale_factor=s, nb=NB)
+    if form is not None:
+        net.set_form(form)
+    return net
 
-direct = []
-_launch = K._launch
-def spy(name, *a):
-    if K._REC is None:
-        direct.append(name)
-    return _launch(name, *a)
-K._launch = spy
-
-def err(f):
-    try:
-        f()
-    except Exception as e:
-        return [type(e).__name__, str(e)]
-    return None
-
-NB = 2
-out = {"default_form": Fh.DENSE_DEFAULT_FORM}
-torch.manual_seed(0)
+out["default_form"] = Fh.DENSE_DEFAULT_FORM
 for form in ("inplace", "composed"):
     for s in (2, 4):
-        del direct[:]
-        net = esrgan.RRDBNet(scale_factor=s, nb=NB).train()
-        net.set_form(form)
-        ts = SRTrainStep(net, precision="x3", image_crit="l1", channels=3)
-        loss = ts.step(torch.rand(4, 4, 16, 64), torch.rand(4, 4, 16 * s, 64 * s))
-        eng = net._engine()
-        assert isinstance(eng, PlainSREngine) and eng.record and tuple(loss.shape) == ()
-        (key, pl), = eng._plans.items()
-        lines = signature(eng._plans)                 # runs every plan: the native executor checks entry point and argument count of every op
-        a, b = ts.pool.ranges[id(net)]
-        out[form + str(s)] = dict(key=[str(k) for k in key], fwd=[o[0] for o in pl["fwd"].ops], bwd=[o[0] for o in pl["bwd"].ops],
-                                  direct=list(direct), sr=list(ts.last_sr.shape), scale=eng.scale, nsig=len(lines),
-                                  pooled=bool(eng.arena.external is not None and b - a == eng.arena.numel),
-                                  sunk=all(p.grad is not None for p in net.parameters()), has_prior=("prior" in pl or "dprior" in pl),
-                                  wrong_hr=err(lambda: ts.step(torch.rand(4, 4, 16, 64), torch.rand(4, 4, 8 * s, 32 * s))))
-
-rec = crnn.CRNN(32, 1, 37, 256).eval()
+        out[form + str(s)] = train_case(lambda: rrdb_net(s, form), s, "l1")
 for s in (2, 4):
-    del direct[:]
-    net = esrgan.RRDBNet(scale_factor=s, nb=NB).eval()
-    ev = TextSREvaluator([net], None, recognizer=rec, channels=3)
-    srs, priors = ev.super_resolve(torch.rand(6, 4, 16, 64))
-    (pl,) = net._engine()._plans.values()
-    out["eval_%%d" %% s] = dict(direct=list(direct), sr=list(srs[0].shape), priors=len(priors), plan=[o[0] for o in pl["fwd"].ops])
-
+    out["eval_%d" % s] = eval_case(lambda: rrdb_net(s), s)
+'''
+EXTRA = r'''
 # odd channel counts: form=None falls back to the composed form
 del direct[:]
 x = torch.rand(1, 5, 7, 6).requires_grad_(True)
@@ -172,19 +116,12 @@ ws = [torch.rand(2 if k < 4 else 6, 6 + 2 * k, 3, 3).requires_grad_(True) for k 
 y = Fh.dense_block(x, ws, None)
 y.sum().backward()
 out["odd"] = dict(direct=list(direct), y=list(y.shape))
-print("RESULT " + json.dumps(out))
 '''
 
 
 @pytest.fixture(scope="module")
 def rec():
-    env = dict(os.environ, TPGSR_PLAN_DRYRUN="1")
-    for k in [k for k in env if k.startswith("TPGSR_") and k != "TPGSR_PLAN_DRYRUN"]:
-        del env[k]
-    r = subprocess.run([sys.executable, "-c", RECORD % dict(root=ROOT, tests=os.path.join(ROOT, "tests"))], capture_output=True, text=True,
-                       env=env, timeout=550)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    return json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    return record(IMPORTS, CASES, EXTRA)
 
 
 NB = 2
@@ -231,18 +168,13 @@ def test_composed_plan_holds_no_window_kernel(rec, scale):
 
 
 def test_l1_criterion_records_its_kernels(rec):
-    for k in ("inplace2", "inplace4", "composed2"):
-        d = rec[k]["direct"]
-        assert "tpgsr_l1_loss_fwd" in d and "tpgsr_l1_loss_bwd" in d
-        assert "tpgsr_charbonnier_loss_fwd" not in d and "tpgsr_image_loss_fwd" not in d
-        assert d.count("tpgsr_copy_strided") == 2          # channels=3: the RGB prefixes of LR and HR
+    check_criterion_kernels(rec, ("inplace2", "inplace4", "composed2"), "l1")
 
 
 def test_evaluator_pass_takes_both_factors(rec):
     for s in (2, 4):
         r = rec[f"eval_{s}"]
-        assert r["sr"] == [6, 3, 16 * s, 64 * s] and r["priors"] == 0
-        assert r["direct"] == ["tpgsr_copy_strided", "tpgsr_copy", "tpgsr_copy"]
+        check_evaluator_case(r, s)
         want = "tpgsr_leaky_relu_window" if rec["default_form"] == "inplace" else "tpgsr_leaky_relu_fwd"
         assert r["plan"].count(want) >= 4 * 3 * NB
 
@@ -254,21 +186,5 @@ def test_odd_channel_counts_take_the_composed_form(rec):
 
 @pytest.mark.parametrize("scale", [2, 4])
 def test_fixtures_load_and_are_finite(scale):
-    from make_golden_rrdb import DEPTHS, N_SMALL, N_STORE
-    from tpgsr_amd.model import esrgan
-    for path in (f"rrdb_x{scale}.npz", f"train_rrdb_x{scale}.npz"):
-        assert os.path.getsize(os.path.join(GOLD, path)) < 700 * 1000, path
-    assert os.path.getsize(os.path.join(GOLD, "rrdb_layouts.json")) < 700 * 1000
-    g = np.load(os.path.join(GOLD, f"rrdb_x{scale}.npz"), allow_pickle=False)
-    t = np.load(os.path.join(GOLD, f"train_rrdb_x{scale}.npz"), allow_pickle=False)
-    for nb in DEPTHS:
-        pre = f"nb{nb}_"
-        assert g[pre + "y"].shape == t[pre + "sr_step0"].shape == (N_STORE[scale], 3, 16 * scale, 64 * scale)
-        assert g[pre + "y_small"].shape == (N_SMALL, 3, 12 * scale, 40 * scale)
-        assert t[pre + "loss"].shape == (2,) and t[pre + "gnorm"].shape == (2,) and (t[pre + "loss"] > 0).all() and (t[pre + "gnorm"] > 0).all()
-        for k in ("y", "y_small", "grad_norms", "grad_heads"):
-            assert np.isfinite(g[pre + k]).all() and g[pre + k].size, k
-        names = [n for n, _ in esrgan.RRDBNet(scale_factor=scale, nb=nb).named_parameters()]
-        assert [str(n) for n in g[pre + "grad_names"]] == names
-        assert (g[pre + "grad_norms"] > 0).all()
-    assert len(g["eval_sr"]) == len(g["eval_lr"]) == len(g["eval_hr"]) == 6
+    import plain_arch_common as P
+    check_fixtures(P.RRDB, scale)
