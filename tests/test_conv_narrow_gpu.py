@@ -141,13 +141,10 @@ def test_weight_gradient_accumulates_onto_a_prefilled_sink():
     fill = torch.randn(w.shape, generator=g)
     wd = w.to(DEV).requires_grad_(True)
     sink = fill.to(DEV).clone()
-    prev, Fh.GRAD_SINK = Fh.GRAD_SINK, {wd.data_ptr(): sink}
-    try:
+    with Fh.grad_sinks({wd.data_ptr(): sink}):
         y = Fh.conv2d_narrow(x.to(DEV).requires_grad_(True), wd, form="narrow")
         y.backward(gy.to(DEV))
         torch.cuda.synchronize()
-    finally:
-        Fh.GRAD_SINK = prev
     assert wd.grad is None
     assert torch.equal(sink.cpu(), fill + plain)             # one fp32 addition per element, on either side
 

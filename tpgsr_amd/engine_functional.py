@@ -14,8 +14,8 @@ Two ways to run it:
   buffers the plan keeps alive -- and from then on a forward or backward pass is one replay of that plan by the native executor
   (csrc/plan.cpp): no Python per operator, no autograd, weight gradients on the weight-gradient stream with ONE batched slab reduce,
   exactly like `CRNNEngine`'s hand-recorded plans.  What makes the trace complete: parameter gradients are accumulated into the arena
-  by the operators' own kernels (`functional.GRAD_SINK`), tensors with two consumers go through `functional.fork` (their gradients are
-  summed by tpgsr_add), so autograd never runs an ATen kernel of its own that a replay would miss -- tests/test_opt_recorded_gpu.py
+  by the operators' own kernels (`functional.grad_sinks`; every operator gets its destination from `functional._grad_dst`, none opts
+  out), tensors with two consumers go through `functional.fork` (their gradients are summed by tpgsr_add), so autograd never runs an ATen kernel of its own that a replay would miss -- tests/test_opt_recorded_gpu.py
   compares replays on fresh inputs with the operator-by-operator run.
 * operator by operator through autograd (the reference implementation of the above; gradients accumulated by autograd into the arena's
   `.grad` views).
@@ -126,17 +126,15 @@ class FunctionalEngine:
         grads = {p.data_ptr(): p.grad for p in self.module.parameters() if p.requires_grad}
         got = []
         h = x.register_hook(got.append) if x is not None else None
-        prev, Fh.GRAD_SINK = Fh.GRAD_SINK, grads
         try:
             # terms_for(role, "bwd"): for the recogniser the number "tpg" gives -- terms_for maps "teacher" to "tpg" outside the x2 policy
             # and returns 2 for either inside it
-            with recording(bwd), K.conv_terms(K.terms_for(role, "bwd")):
+            with Fh.grad_sinks(grads), recording(bwd), K.conv_terms(K.terms_for(role, "bwd")):
                 torch.autograd.backward(res, dres)
                 if bwd.deferred is not None:
                     K.flush_wgrad_reduces()
                 K._REC.join()
         finally:
-            Fh.GRAD_SINK = prev
             if h is not None:
                 h.remove()
         out.update({"bwd": bwd, self.DOUT: dres})

@@ -12,6 +12,7 @@ module boundary.  Parameters keep the PyTorch layouts (state_dict interchange); 
 not the tuned hot path).  Nothing here falls back to a stock PyTorch kernel: non-CUDA inputs raise."""
 from __future__ import annotations
 
+from contextlib import contextmanager, nullcontext
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -39,11 +40,78 @@ def _new(like, *shape):
 # Parameter-gradient sinks (engine_functional.py, recorded mode): data_ptr of a parameter -> the fp32 buffer its gradient is ACCUMULATED
 # into by the operator's own backward kernels (the slab reduce / the BatchNorm-backward finalize with accumulate = 1).  The backward then
 # hands autograd `None` for that parameter: no AccumulateGrad node runs, i.e. no ATen `add_` that a recorded plan could not replay.
+# Installed by grad_sinks(), read by _grad_dst() alone.
 GRAD_SINK: dict = {}
 
 
-def _sink(p):
-    return GRAD_SINK.get(p.data_ptr()) if (GRAD_SINK and p is not None) else None
+@contextmanager
+def grad_sinks(mapping: dict):
+    """`mapping` is the sink table inside the block; the previous table comes back after it"""
+    global GRAD_SINK
+    prev, GRAD_SINK = GRAD_SINK, mapping
+    try:
+        yield mapping
+    finally:
+        GRAD_SINK = prev
+
+
+def _grad_dst(*ps):
+    """Where the gradients of a parameter and of those reduced by the same launch (its bias / beta; None entries stay None) go
+    -> (destinations, accumulate, what the backward hands autograd): the sinks, accumulated into, and None for autograd where the first
+    parameter has a sink; fresh tensors, overwritten and returned, otherwise.  Every operator with a parameter asks here."""
+    sinks = [None if p is None else GRAD_SINK.get(p.data_ptr()) for p in ps]
+    if sinks[0] is None:
+        fresh = tuple(None if p is None else torch.empty_like(p, memory_format=torch.contiguous_format) for p in ps)
+        return fresh, False, fresh
+    if any(s is None for s, p in zip(sinks, ps) if p is not None):
+        raise RuntimeError("a sunk weight gradient needs its bias gradient sunk too")
+    return tuple(sinks), True, (None,) * len(ps)
+
+
+def _conv_wgrad(g, x, dy, w, b=None, *, in_ld=None, in_coff=0, dy_ld=None, dy_coff=0, dy_ps=False, layout=0, gscale=1.0, geom_splits=True,
+                staged=None):
+    """Weight (and bias) gradient of convolution `g` over input x and output gradient dy -> (dw, db) for autograd (None where sunk).
+    Slabs and reduce are a leaf of the graph: on the weight-gradient stream when a recorded plan overlaps them (K.side() is a no-op
+    eagerly).  in_* / dy_*: the windows of x / dy the convolution ran on.  geom_splits=False: the legacy split count (the BiGRU's 1x1
+    products).  staged = (buffer, finish): the slabs are reduced into `buffer` at once, not in the plan's batched reduce, and
+    finish(destination, accumulate) reads it next on the same stream (the sub-pixel transposed convolution's fold)."""
+    Z = K.wgrad_splits(g.M, g.K, g.Cout, geom=g if geom_splits else None)
+    part = _new(x, Z, g.K, g.Cout)
+    dbp = _new(x, Z, g.Cout) if b is not None else None
+    dst, acc, ret = _grad_dst(w, b)
+    with K.side():
+        K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, x, in_ld=in_ld, in_coff=in_coff), dy, part, dbp, dy_ld=dy_ld, dy_coff=dy_coff,
+                                       dy_ps=dy_ps, zsplits=Z if geom_splits else 0))
+        if staged is None:
+            K.wgrad_reduce(part, dbp, Z, g, *dst, layout=layout, accumulate=acc, gscale=gscale)
+        else:
+            K.wgrad_reduce(part, None, Z, g, staged[0], None, layout=layout, accumulate=False, gscale=gscale, defer=False)
+            staged[1](dst[0], acc)
+    return ret
+
+
+def _partials_grad(p, part, rows, n, launch=None):
+    """partial sums part [rows][n] -> the gradient of parameter p for autograd (None where sunk).  launch: the kernel that fills `part`; it
+    and the reduce are a side-stream section like _conv_wgrad's.  None: they are there already and the reduce stays on the caller's
+    stream (PReLU: its backward kernel writes them next to dx)."""
+    (dst,), acc, (ret,) = _grad_dst(p)
+    with (K.side() if launch is not None else nullcontext()):
+        if launch is not None:
+            launch()
+        K.reduce_partials(part, rows, n, dst, accumulate=acc)
+    return ret
+
+
+def _choose_form(op, form, forms, default, unfit, hint=" or None"):
+    """the `form=` argument of a wrapper with several routes -> the form to run.  An unknown name raises; None is `default`; `unfit` maps
+    the forms these arguments have no route in to the reason, which raises when one of them is what would run."""
+    if form is None:
+        form = default
+    elif form not in forms:
+        raise ValueError(f"{op}: form={form!r}, expected one of {forms}{hint}")
+    if form in unfit:
+        raise ValueError(f"{op}: {unfit[form]}")
+    return form
 
 
 def _c(t):
@@ -127,35 +195,21 @@ class _Conv2d(torch.autograd.Function):
             raise ValueError("conv2d: empty output")
         out = _new(x, N, 2 * g.OH, 2 * g.OW, Cout // 4) if out_ps else _new(x, N, g.OH, g.OW, Cout)
         K.conv_fwd(K.make_conv_args(g, x, wt_f, out, bias=b, out_ps=out_ps))
-        ctx.save_for_backward(x, w, wt_d)
-        ctx.cfg = (g, out_ps, transposed, wscale, b is not None)
-        ctx.bias_ptr = b.data_ptr() if b is not None else None     # (the sinks are looked up when the backward runs)
+        ctx.save_for_backward(x, w, wt_d, b)
+        ctx.cfg = (g, out_ps, transposed, wscale)
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        x, w, wt_d = ctx.saved_tensors
-        g, out_ps, transposed, wscale, has_b = ctx.cfg
+        x, w, wt_d, b = ctx.saved_tensors
+        g, out_ps, transposed, wscale = ctx.cfg
         dy = _c(dy)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = _new(x, g.N, g.H, g.W, g.Cin)
             K.conv_fwd(K.make_conv_args(g.dgrad(), dy, wt_d, dx, in_ps=out_ps))
-        if ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]):
-            Z = K.wgrad_splits(g.M, g.K, g.Cout, geom=g)
-            part = _new(x, Z, g.K, g.Cout)
-            dbp = _new(x, Z, g.Cout) if has_b else None
-            sw = _sink(w)
-            with K.side():      # a leaf of the graph: on the weight-gradient stream when a recorded plan overlaps them (no-op eagerly)
-                K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, x), dy, part, dbp, dy_ps=out_ps, zsplits=Z))
-                if sw is not None:
-                    sb = GRAD_SINK.get(ctx.bias_ptr) if has_b else None
-                    assert not has_b or sb is not None, "a sunk weight gradient needs its bias gradient sunk too"
-                    K.wgrad_reduce(part, dbp, Z, g, sw, sb, layout=1 if transposed else 0, accumulate=True, gscale=wscale)
-                else:
-                    dw = torch.empty_like(w)
-                    db = _new(x, g.Cout) if has_b else None
-                    K.wgrad_reduce(part, dbp, Z, g, dw, db, layout=1 if transposed else 0, accumulate=False, gscale=wscale)
+        if ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[2]):
+            dw, db = _conv_wgrad(g, x, dy, w, b, dy_ps=out_ps, layout=1 if transposed else 0, gscale=wscale)
         return dx, dw, db, None, None, None, None, None
 
 
@@ -270,18 +324,9 @@ class _TConvK4S2SubPixel(torch.autograd.Function):
             dx = _new(x, g.N, g.H, g.W, g.Cin)
             K.conv_fwd(K.make_conv_args(g.dgrad(), dy, wt_d, dx, in_ps=True))
         if ctx.needs_input_grad[1]:
-            Z = K.wgrad_splits(g.M, g.K, g.Cout, geom=g)
-            part = _new(x, Z, g.K, g.Cout)
             dw3 = _new(x, 4 * Cout, Cin, 3, 3)
-            sw = _sink(w)
-            with K.side():
-                K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, x), dy, part, None, dy_ps=True, zsplits=Z))
-                K.wgrad_reduce(part, None, Z, g, dw3, None, layout=0, accumulate=False, defer=False)
-                if sw is not None:
-                    K.tconv4s2_fold_grad(dw3, Cin, Cout, sw, accumulate=True)
-                else:
-                    dw = torch.empty_like(w, memory_format=torch.contiguous_format)
-                    K.tconv4s2_fold_grad(dw3, Cin, Cout, dw, accumulate=False)
+            dw, _ = _conv_wgrad(g, x, dy, w, dy_ps=True,
+                                staged=(dw3, lambda dst, acc: K.tconv4s2_fold_grad(dw3, Cin, Cout, dst, accumulate=acc)))
         return dx, dw
 
 
@@ -314,14 +359,7 @@ class _TConvK4S2Small(torch.autograd.Function):
             nblk = max(1, min(_TConvK4S2Small.NBLK, (N * H * W + 63) // 64))
             E = Cin * Cout * 16
             part = _new(x, nblk, E)
-            sw = _sink(w)
-            with K.side():
-                K.tconv4s2_small_bwd_weight(x, dy, N, H, W, Cin, Cout, part, nblk)
-                if sw is not None:
-                    K.reduce_partials(part, nblk, E, sw, accumulate=True)
-                else:
-                    dw = torch.empty_like(w)
-                    K.reduce_partials(part, nblk, E, dw, accumulate=False)
+            dw = _partials_grad(w, part, nblk, E, lambda: K.tconv4s2_small_bwd_weight(x, dy, N, H, W, Cin, Cout, part, nblk))
         return dx, dw
 
 
@@ -349,12 +387,8 @@ def conv_transpose2d_k4s2(x, w, form: Optional[str] = None):
     if x.dim() != 4 or x.shape[-1] != Cin:
         raise ValueError(f"conv_transpose2d_k4s2: input {tuple(x.shape)} is not (N, H, W, {Cin})")
     auto = tconv_k4s2_form(Cin, Cout)
-    if form is None:
-        form = auto
-    elif form not in TCONV_FORMS:
-        raise ValueError(f"conv_transpose2d_k4s2: form={form!r}, expected one of {TCONV_FORMS}")
-    elif form != "dilated" and form != auto:
-        raise ValueError(f"conv_transpose2d_k4s2: no {form} route for {Cin} -> {Cout} channels")
+    unfit = {f: f"no {f} route for {Cin} -> {Cout} channels" for f in ("direct", "subpixel") if f != auto}
+    form = _choose_form("conv_transpose2d_k4s2", form, TCONV_FORMS, auto, unfit, hint="")
     if form == "direct":
         return _TConvK4S2Small.apply(x, w)
     if form == "subpixel":
@@ -389,14 +423,13 @@ class _BatchNorm(torch.autograd.Function):
             K.bn_finalize(None, 0, C, 0, None, gamma, beta, rm, rv, scale, shift, momentum=momentum, eps=eps, eval_mode=True)
         out = torch.empty_like(x)
         K.affine_act(x, M, C, scale, shift, act, out)
-        ctx.save_for_backward(x, gamma, scale, shift, mean, rstd)
+        ctx.save_for_backward(x, gamma, beta, scale, shift, mean, rstd)
         ctx.cfg = (training, act, M, C)
-        ctx.beta_ptr = beta.data_ptr()
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        x, gamma, scale, shift, mean, rstd = ctx.saved_tensors
+        x, gamma, beta, scale, shift, mean, rstd = ctx.saved_tensors
         training, act, M, C = ctx.cfg
         if not training:
             raise RuntimeError("backward through an eval-mode BatchNorm is not supported (the reference only trains in train mode)")
@@ -405,15 +438,9 @@ class _BatchNorm(torch.autograd.Function):
         nblk = max(1, min(1024, M // 64))
         part = torch.empty(nblk, 2, C, device=dev)
         coef = torch.empty(3, C, device=dev)
-        sg, sb = _sink(gamma), GRAD_SINK.get(ctx.beta_ptr)
+        dst, acc, (dgamma, dbeta) = _grad_dst(gamma, beta)
         K.bn_bwd_reduce(dy, None, x, M, C, scale, shift, mean, rstd, act, part, nblk)
-        if sg is not None:
-            assert sb is not None, "a sunk BatchNorm weight gradient needs its bias gradient sunk too"
-            dgamma = dbeta = None
-            K.bn_bwd_finalize(part, nblk, C, M, gamma, mean, rstd, sg, sb, coef, accumulate=True)
-        else:
-            dgamma, dbeta = torch.empty(C, device=dev), torch.empty(C, device=dev)
-            K.bn_bwd_finalize(part, nblk, C, M, gamma, mean, rstd, dgamma, dbeta, coef, accumulate=False)
+        K.bn_bwd_finalize(part, nblk, C, M, gamma, mean, rstd, *dst, coef, accumulate=acc)
         dx = torch.empty_like(x)
         K.bn_bwd_apply(dy, None, x, M, C, scale, shift, act, coef, dx)
         return dx, dgamma, dbeta, None, None, None, None, None, None
@@ -503,13 +530,7 @@ class _PReLU(torch.autograd.Function):
         dx = torch.empty_like(x)
         dap = torch.empty(nb, device=x.device)
         K.prelu_bwd(x, alpha, _c(dy), None, x.numel(), dx, dap, nb)
-        sa = _sink(alpha)
-        if sa is not None:
-            K.reduce_partials(dap, nb, 1, sa, accumulate=True)
-            return dx, None
-        da = torch.empty(1, device=x.device)
-        K.reduce_partials(dap, nb, 1, da, accumulate=False)
-        return dx, da
+        return dx, _partials_grad(alpha, dap, nb, 1)
 
 
 def prelu(x, alpha):
@@ -675,54 +696,34 @@ class _DenseBlock(torch.autograd.Function):
         K.scaled_add(y, nf, 0, D, Ct, 0, res_scale, y, nf, 0, M, nf)      # in place on x5: the backward needs D only
         geoms.append(g)
         wds.append(wt_d)
-        ctx.save_for_backward(D, *ws, *wds)
+        ctx.save_for_backward(D, *ws, *wds, *bs)
         ctx.cfg = (geoms, slope, res_scale, nf, gc)
-        ctx.bias_ptrs = [None if b is None else b.data_ptr() for b in bs]
         return y
-
-    @staticmethod
-    def _wgrad(ctx, k, g, w, D, Ct, dy, dy_ld, dy_coff):
-        """weight / bias gradient of convolution k exactly as _Conv2d.backward: slabs on the side stream, reduced into the sink or a tensor"""
-        has_b = ctx.bias_ptrs[k] is not None
-        if not (ctx.needs_input_grad[3 + k] or (has_b and ctx.needs_input_grad[8 + k])):
-            return None, None
-        dw = db = None
-        Z = K.wgrad_splits(g.M, g.K, g.Cout, geom=g)
-        part = _new(D, Z, g.K, g.Cout)
-        dbp = _new(D, Z, g.Cout) if has_b else None
-        sw = _sink(w)
-        with K.side():
-            K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, D, in_ld=Ct), dy, part, dbp, dy_ld=dy_ld, dy_coff=dy_coff, zsplits=Z))
-            if sw is not None:
-                sb = GRAD_SINK.get(ctx.bias_ptrs[k]) if has_b else None
-                assert not has_b or sb is not None, "a sunk weight gradient needs its bias gradient sunk too"
-                K.wgrad_reduce(part, dbp, Z, g, sw, sb, layout=0, accumulate=True)
-            else:
-                dw = torch.empty_like(w)
-                db = _new(D, g.Cout) if has_b else None
-                K.wgrad_reduce(part, dbp, Z, g, dw, db, layout=0, accumulate=False)
-        return dw, db
 
     @staticmethod
     def backward(ctx, dy):
         D, *rest = ctx.saved_tensors
-        ws, wds = rest[:5], rest[5:]
+        ws, wds, bs = rest[:5], rest[5:10], rest[10:]
         geoms, slope, res_scale, nf, gc = ctx.cfg
         dy = _c(dy)
         N, H, W, Ct = D.shape
         M = N * H * W
         dws, dbs = [None] * 5, [None] * 5
+
+        def wgrad(k, dy, dy_ld=None, dy_coff=0):
+            if ctx.needs_input_grad[3 + k] or (bs[k] is not None and ctx.needs_input_grad[8 + k]):
+                dws[k], dbs[k] = _conv_wgrad(geoms[k], D, dy, ws[k], bs[k], in_ld=Ct, dy_ld=dy_ld, dy_coff=dy_coff)
         dx5 = torch.empty_like(dy)
         K.scaled_add(dy, nf, 0, None, 0, 0, res_scale, dx5, nf, 0, M, nf)
         G = _new(D, N, H, W, Ct)
         K.conv_fwd(K.make_conv_args(geoms[4].dgrad(), dx5, wds[4], G))
-        dws[4], dbs[4] = _DenseBlock._wgrad(ctx, 4, geoms[4], ws[4], D, Ct, dx5, None, 0)
+        wgrad(4, dx5)
         T = None
         for k in (3, 2, 1, 0):
             g = geoms[k]
             Cin = g.Cin
             K.dense_bwd_step(G, Ct, T, Cin + gc, D, Cin, gc, slope, M)      # (k = 3: mask only, every column of G is conv5's alone so far)
-            dws[k], dbs[k] = _DenseBlock._wgrad(ctx, k, g, ws[k], D, Ct, G, Ct, Cin)
+            wgrad(k, G, Ct, Cin)
             T = _new(D, N, H, W, Cin)
             K.conv_fwd(K.make_conv_args(g.dgrad(), G, wds[k], T, in_ld=Ct, in_coff=Cin))
         dx = torch.empty_like(dy)
@@ -747,8 +748,6 @@ def dense_block(x, weights, biases=None, slope: float = 0.2, res_scale: float = 
     [gc | nf][nf + k gc][3][3], biases = five vectors, or None entries / None.  form "inplace": the block on one concatenation buffer
     (_DenseBlock; channel counts that are multiples of 4); "composed": the same mathematics over fork / cat / conv2d / leaky_relu;
     None: in place where the channel counts allow it, composed otherwise."""
-    if form is not None and form not in DENSE_FORMS:
-        raise ValueError(f"dense_block: form={form!r}, expected one of {DENSE_FORMS} or None")
     ws = list(weights)
     bs = [None] * 5 if biases is None else list(biases)
     if len(ws) != 5 or len(bs) != 5:
@@ -761,10 +760,8 @@ def dense_block(x, weights, biases=None, slope: float = 0.2, res_scale: float = 
         if tuple(w.shape) != want:
             raise ValueError(f"dense_block: weight {k + 1} is {tuple(w.shape)}, expected {want}")
     fits = nf % 4 == 0 and gc % 4 == 0
-    if form is None:
-        form = DENSE_DEFAULT_FORM if fits else "composed"
-    elif form == "inplace" and not fits:
-        raise ValueError(f"dense_block: the in-place form takes channel counts that are multiples of 4, got nf {nf}, gc {gc}")
+    unfit = {} if fits else {"inplace": f"the in-place form takes channel counts that are multiples of 4, got nf {nf}, gc {gc}"}
+    form = _choose_form("dense_block", form, DENSE_FORMS, DENSE_DEFAULT_FORM if fits else "composed", unfit)
     if form == "composed":
         return _dense_block_composed(x, ws, bs, float(slope), float(res_scale))
     return _DenseBlock.apply(x, float(slope), float(res_scale), *ws, *bs)
@@ -775,23 +772,6 @@ DENSE_DEFAULT_FORM = "inplace"
 
 
 # ---- residual block (EDSR's _Residual_Block, model/edsr.py:18-32) -------------------------------------------------------------------
-def _wgrad3(g, x, dy, w):
-    """weight gradient of a bias-free convolution exactly as _Conv2d.backward: slabs on the side stream, reduced into the sink (-> None) or
-    into a tensor of its own"""
-    Z = K.wgrad_splits(g.M, g.K, g.Cout, geom=g)
-    part = _new(x, Z, g.K, g.Cout)
-    sw = _sink(w)
-    dw = None
-    with K.side():
-        K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, x), dy, part, None, zsplits=Z))
-        if sw is not None:
-            K.wgrad_reduce(part, None, Z, g, sw, None, layout=0, accumulate=True)
-        else:
-            dw = torch.empty_like(w)
-            K.wgrad_reduce(part, None, Z, g, dw, None, layout=0, accumulate=False)
-    return dw
-
-
 class _ResBlock(torch.autograd.Function):
     """y = res_scale * conv2(relu(conv1(x))) + x, two bias-free 3x3 convolutions over C channels (a multiple of 4).
 
@@ -835,7 +815,7 @@ class _ResBlock(torch.autograd.Function):
         gr = torch.empty_like(dy)
         K.scaled_add(dy, C_, 0, None, 0, 0, res_scale, gr, C_, 0, M, C_)
         if ctx.needs_input_grad[2]:
-            dw2 = _wgrad3(g, h, gr, w2)
+            dw2, _ = _conv_wgrad(g, h, gr, w2)
         dz = torch.empty_like(dy)
         if K.bnb_fusable(C_) and getattr(wd2, "_tpgsr_twin", None) is not None:
             K.conv_fwd(K.make_conv_args(g.dgrad(), gr, wd2, dz, bnb=dict(y=h, act="relu", store_dz=True)))
@@ -843,7 +823,7 @@ class _ResBlock(torch.autograd.Function):
             K.conv_fwd(K.make_conv_args(g.dgrad(), gr, wd2, dz))
             K.act_bwd(h, dz, dz.numel(), "relu", dz)
         if ctx.needs_input_grad[1]:
-            dw1 = _wgrad3(g, x, dz, w1)
+            dw1, _ = _conv_wgrad(g, x, dz, w1)
         if ctx.needs_input_grad[0]:
             T = torch.empty_like(dy)
             K.conv_fwd(K.make_conv_args(g.dgrad(), dz, wd1, T))
@@ -866,8 +846,6 @@ def res_block(x, w1, w2, res_scale: float = 0.1, form: Optional[str] = None):
     bias-free 3x3 convolution weights [C][C][3][3].  form "fused": one operator with a hand-written backward (_ResBlock; C a multiple
     of 4); "composed": the same mathematics over fork / conv2d / relu / scaled_add; None: RES_DEFAULT_FORM (the composed form, see there)
     where the channel count allows it, composed otherwise.  The two forms give the same bits.  Every refusal comes before a launch."""
-    if form is not None and form not in RES_FORMS:
-        raise ValueError(f"res_block: form={form!r}, expected one of {RES_FORMS} or None")
     if x.dim() != 4:
         raise ValueError(f"res_block: input {tuple(x.shape)} is not (N, H, W, C)")
     C_ = x.shape[-1]
@@ -877,10 +855,8 @@ def res_block(x, w1, w2, res_scale: float = 0.1, form: Optional[str] = None):
         if tuple(w.shape[:2]) != (C_, C_):
             raise ValueError(f"res_block: input has {C_} channels, weight {k + 1} is {tuple(w.shape)}")
     fits = C_ % 4 == 0
-    if form is None:
-        form = RES_DEFAULT_FORM if fits else "composed"
-    elif form == "fused" and not fits:
-        raise ValueError(f"res_block: the fused form takes a channel count that is a multiple of 4, got {C_} (use form='composed')")
+    unfit = {} if fits else {"fused": f"the fused form takes a channel count that is a multiple of 4, got {C_} (use form='composed')"}
+    form = _choose_form("res_block", form, RES_FORMS, RES_DEFAULT_FORM if fits else "composed", unfit)
     if form == "composed":
         return _res_block_composed(x, w1, w2, float(res_scale))
     return _ResBlock.apply(x, w1, w2, float(res_scale))
@@ -923,14 +899,7 @@ class _Conv2dNarrow(torch.autograd.Function):
             nblk = K.narrow_wgrad_blocks(N, H, W)
             E = Cout * Cin * 9
             part = _new(x, nblk, E)
-            sw = _sink(w)
-            with K.side():
-                K.conv3x3_narrow_bwd_weight(x, dy, N, H, W, Cin, Cout, part, nblk)
-                if sw is not None:
-                    K.reduce_partials(part, nblk, E, sw, accumulate=True)
-                else:
-                    dw = torch.empty_like(w)
-                    K.reduce_partials(part, nblk, E, dw, accumulate=False)
+            dw = _partials_grad(w, part, nblk, E, lambda: K.conv3x3_narrow_bwd_weight(x, dy, N, H, W, Cin, Cout, part, nblk))
         return dx, dw
 
 
@@ -940,20 +909,15 @@ NARROW_FORMS = ("narrow", "matrix")
 def conv2d_narrow(x, w, form: Optional[str] = None):
     """nn.Conv2d(Cin, Cout <= 4, 3, padding=1, bias=False) on an NHWC map.  form "narrow": the direct kernels (Cin a multiple of 4 up to
     256); "matrix": conv2d(x, w, None, 1), the matrix-core route with Cout padded to a tile; None: NARROW_DEFAULT_FORM."""
-    if form is not None and form not in NARROW_FORMS:
-        raise ValueError(f"conv2d_narrow: form={form!r}, expected one of {NARROW_FORMS} or None")
     if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or not 1 <= w.shape[0] <= K.NARROW_MAX_COUT:
         raise ValueError(f"conv2d_narrow: a [Cout <= {K.NARROW_MAX_COUT}][Cin][3][3] weight, got {tuple(w.shape)}")
     Cin = w.shape[1]
     if x.dim() != 4 or x.shape[-1] != Cin:
         raise ValueError(f"conv2d_narrow: input {tuple(x.shape)} is not (N, H, W, {Cin})")
-    if form is None:
-        form = NARROW_DEFAULT_FORM
-    if form == "matrix":
+    unfit = {"narrow": f"the direct kernels take an input channel count that is a multiple of 4 up to {K.NARROW_MAX_CIN}, "
+                       f"got {Cin} (use form='matrix')"} if (Cin % 4 or not 4 <= Cin <= K.NARROW_MAX_CIN) else {}
+    if _choose_form("conv2d_narrow", form, NARROW_FORMS, NARROW_DEFAULT_FORM, unfit) == "matrix":
         return conv2d(x, w, None, 1)
-    if Cin % 4 or not 4 <= Cin <= K.NARROW_MAX_CIN:
-        raise ValueError(f"conv2d_narrow: the direct kernels take an input channel count that is a multiple of 4 up to {K.NARROW_MAX_CIN}, "
-                         f"got {Cin} (use form='matrix')")
     return _Conv2dNarrow.apply(x, w)
 
 
@@ -1080,25 +1044,19 @@ class _GruProj(torch.autograd.Function):
             wt_f, wt_d, *_ = _pack(w.reshape(G, Cin, 1, 1), False, 1.0)
             K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, Cin, G), x, wt_f, gi, bias=b, out_ld=2 * G, out_coff=d * G))
             packs.append(wt_d)
-        ctx.save_for_backward(x, *packs)
+        ctx.save_for_backward(x, *packs, w0, w1, b0, b1)
         ctx.cfg = (N, H, W, Cin, G)
         return gi
 
     @staticmethod
     def backward(ctx, dgi):
-        x, wd0, wd1 = ctx.saved_tensors
+        x, wd0, wd1, w0, w1, b0, b1 = ctx.saved_tensors
         N, H, W, Cin, G = ctx.cfg
         dgi = _c(dgi)
         outs = []
         dx = None
-        for d, wt_d in enumerate((wd0, wd1)):
-            g = ConvGeom(N, H, W, Cin, G)
-            Z = K.wgrad_splits(g.M, g.K, G)
-            part, dbp = _new(x, Z, g.K, G), _new(x, Z, G)
-            K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(g, x), dgi, part, dbp, dy_ld=2 * G, dy_coff=d * G))
-            dw, db = _new(x, G, Cin), _new(x, G)
-            K.wgrad_reduce(part, dbp, Z, g, dw, db, accumulate=False)
-            outs.append((dw, db))
+        for d, (wt_d, w, b) in enumerate(((wd0, w0, b0), (wd1, w1, b1))):
+            outs.append(_conv_wgrad(ConvGeom(N, H, W, Cin, G), x, dgi, w, b, dy_ld=2 * G, dy_coff=d * G, geom_splits=False))
             if ctx.needs_input_grad[0]:
                 t = _new(x, N, H, W, Cin)
                 K.conv_fwd(K.make_conv_args(ConvGeom(N, H, W, G, Cin), dgi, wt_d, t, in_ld=2 * G, in_coff=d * G))
@@ -1130,13 +1088,13 @@ class _GruCore(torch.autograd.Function):
         h = _new(gi, N, H, W, 2 * U)
         gates = _new(gi, N, H, W, 8 * U)
         K.bigru_fwd(gi, whh, bhh, N, H, W, axis, h, gates, hidden=U)
-        ctx.save_for_backward(gates, h, whh)
+        ctx.save_for_backward(gates, h, whh, whh0, whh1, bhh0, bhh1)
         ctx.cfg = (N, H, W, axis, U)
         return h
 
     @staticmethod
     def backward(ctx, dh):
-        gates, h, whh = ctx.saved_tensors
+        gates, h, whh, *params = ctx.saved_tensors
         N, H, W, axis, U = ctx.cfg
         dgi, dgh = _new(h, N, H, W, 6 * U), _new(h, N, H, W, 6 * U)
         K.bigru_bwd(gates, h, _c(dh), None, whh, N, H, W, axis, dgi, dgh, hidden=U)
@@ -1145,12 +1103,8 @@ class _GruCore(torch.autograd.Function):
             sgn = 1 if d == 0 else -1
             # dW_hh[d] = dgh[:, d]^T h_prev(d): h shifted one step against the scan direction (engine.GruLayer.bwd)
             gh = ConvGeom(N, H, W, U, 3 * U, 1, 1, sgn if axis == 1 else 0, sgn if axis == 0 else 0, H, W)
-            Z = K.wgrad_splits(gh.M, gh.K, 3 * U)
-            part, dbp = _new(h, Z, U, 3 * U), _new(h, Z, 3 * U)
-            K.conv_wgrad(K.make_wgrad_args(K.make_conv_args(gh, h, in_ld=2 * U, in_coff=U * d), dgh, part, dbp, dy_ld=6 * U, dy_coff=3 * U * d))
-            dw, db = _new(h, 3 * U, U), _new(h, 3 * U)
-            K.wgrad_reduce(part, dbp, Z, gh, dw, db, accumulate=False)
-            res.append((dw, db))
+            res.append(_conv_wgrad(gh, h, dgh, params[d], params[2 + d], in_ld=2 * U, in_coff=U * d, dy_ld=6 * U, dy_coff=3 * U * d,
+                                   geom_splits=False))
         return dgi, res[0][0], res[1][0], res[0][1], res[1][1], None
 
 
