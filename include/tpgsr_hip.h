@@ -699,6 +699,24 @@ int tpgsr_conv3x3_narrow_bwd_weight(const float* x, const float* dy, int N, int 
                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Direct 5x5, pad 2, stride 1 convolution to 1 <= Cout <= 4 channels, NHWC, optional bias (csrc/conv_narrow5.hip) -- SRCNN's conv3
+ * (reference model/srcnn.py, Conv2d(32, 3, 5, padding=2) on the HR grid).  x [N][H][W][Cin], w [Cout][Cin][5][5] as PyTorch stores it
+ * (nothing is packed), bias [Cout] or NULL, y / dy [N][H][W][Cout].  Cin is a multiple of 4 from 4 to 64 (the weights are staged in LDS
+ * once per workgroup; a lane owns output elements); anything else, a null pointer or N H W >= 2^27 is refused before a launch.  Plain
+ * fp32 fused multiply-adds in a fixed order (no atomics, bitwise reproducible; the arithmetic policy of the matrix-core routes does not
+ * apply).  x and dx move in 16-byte accesses when their pointers are 16-byte aligned, element by element (the same bits) otherwise.
+ * Nothing outside the outputs is written.
+ * _bwd_weight writes partial [nblk][Cout Cin 25 + Cout]: a row holds the weight elements in w's order, then the bias gradient
+ * (workgroup b sums its range of pixels in order; workgroups behind the last pixel write zeros), finished by
+ * tpgsr_reduce_partials(partial, nblk, Cout Cin 25 + Cout, dw | db, accumulate).
+ * ---------------------------------------------------------------------------------------------- */
+int tpgsr_conv5x5_narrow_fwd(const float* x, const float* w, const float* bias, int N, int H, int W, int Cin, int Cout, float* y,
+                             void* stream);
+int tpgsr_conv5x5_narrow_bwd_data(const float* dy, const float* w, int N, int H, int W, int Cin, int Cout, float* dx, void* stream);
+int tpgsr_conv5x5_narrow_bwd_weight(const float* x, const float* dy, int N, int H, int W, int Cin, int Cout, float* partial, int nblk,
+                                    void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Tail: out = tanh(bias + sum_kw P[h][w+kw-4][kw][co])  (model/tsrn.py:159,213), NCHW output
  * ---------------------------------------------------------------------------------------------- */
 int tpgsr_tail_shiftsum_tanh(const float* P, const float* bias, int N, int H, int W, int Co, int KS,

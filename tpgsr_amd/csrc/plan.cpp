@@ -84,6 +84,7 @@ const std::unordered_map<std::string, Entry>& registry() {
       TPGSR_REG(tpgsr_leaky_relu_bwd), TPGSR_REG(tpgsr_charbonnier_loss_fwd), TPGSR_REG(tpgsr_charbonnier_loss_bwd),
       TPGSR_REG(tpgsr_leaky_relu_window), TPGSR_REG(tpgsr_scaled_add), TPGSR_REG(tpgsr_dense_bwd_step),
       TPGSR_REG(tpgsr_conv3x3_narrow_fwd), TPGSR_REG(tpgsr_conv3x3_narrow_bwd_data), TPGSR_REG(tpgsr_conv3x3_narrow_bwd_weight),
+      TPGSR_REG(tpgsr_conv5x5_narrow_fwd), TPGSR_REG(tpgsr_conv5x5_narrow_bwd_data), TPGSR_REG(tpgsr_conv5x5_narrow_bwd_weight),
   };
   return r;
 }

@@ -282,8 +282,8 @@ class FunctionalSREngine(FunctionalEngine):
 
 
 class PlainSREngine(FunctionalSREngine):
-    """`FunctionalSREngine` for a backbone WITHOUT a text prior: the reference's prior-free baselines (`--arch srres | rdn | vdsr | lapsrn | esrgan | edsr`,
-    model/{srresnet,rdn,vdsr,lapsrn,esrgan,edsr}.py SRResNet / RDN / VDSR / LapSRN / RRDBNet / EDSR), which the `else:` branch of the train loop (interfaces/super_resolution.py:409-424)
+    """`FunctionalSREngine` for a backbone WITHOUT a text prior: the reference's prior-free baselines (`--arch srres | rdn | vdsr | lapsrn | esrgan | edsr | srcnn`,
+    model/{srresnet,rdn,vdsr,lapsrn,esrgan,edsr,srcnn}.py SRResNet / RDN / VDSR / LapSRN / RRDBNet / EDSR / SRCNN), which the `else:` branch of the train loop (interfaces/super_resolution.py:409-424)
     trains with `model(images_lr[:, :channel_num])`.  `SRTrainStep`, `FusedAdam`, `ArenaPool` and `TextSREvaluator` drive the module
     through this adapter; `module(x)` under autograd keeps working on its own.
 

@@ -102,6 +102,26 @@ def _partials_grad(p, part, rows, n, launch=None):
     return ret
 
 
+def _row_partials_grad(ps, part, rows, n, launch):
+    """_partials_grad for ONE kernel that leaves the partial sums of several parameters in one row -- part [rows][n] holds the gradients
+    of `ps` one behind another (a weight, then its bias; trailing columns of an absent parameter are dropped) -> a tuple for autograd
+    (None where sunk).  The parameters' destinations are separate tensors and tpgsr_reduce_partials writes a row to one place (its row
+    length is its row stride), so the row is reduced into a buffer of its own and one launch per parameter carries its slice on: a
+    tpgsr_add into a sink, a tpgsr_copy into a fresh tensor.  One pass over the pixels for all of them is what the shared row buys."""
+    dst, acc, ret = _grad_dst(*ps)
+    row = _new(part, n)
+    offs = [sum(q.numel() for q in ps[:i]) for i in range(len(ps))]
+    with K.side():
+        launch()
+        K.reduce_partials(part, rows, n, row, accumulate=False)
+        for q, o, d in zip(ps, offs, dst):
+            if acc:
+                K.add(d, row[o:o + q.numel()], q.numel(), d)
+            else:
+                K.copy(row[o:o + q.numel()], d, q.numel())
+    return ret
+
+
 def _choose_form(op, form, forms, default, unfit, hint=" or None"):
     """the `form=` argument of a wrapper with several routes -> the form to run.  An unknown name raises; None is `default`; `unfit` maps
     the forms these arguments have no route in to the reason, which raises when one of them is what would run."""
@@ -923,6 +943,64 @@ def conv2d_narrow(x, w, form: Optional[str] = None):
 
 # the form `form=None` runs: decided by tools/lab/edsr_step_time.py (profiles/edsr_step_time.md)
 NARROW_DEFAULT_FORM = "narrow"
+
+
+# ---- direct 5x5 convolution to <= 4 channels, optional bias (SRCNN's conv3, model/srcnn.py) -----------------------------------------
+class _Conv2dNarrow5(torch.autograd.Function):
+    """5x5 pad-2 convolution to 1 .. 4 output channels on the direct kernels (csrc/conv_narrow5.hip): the weight is read as PyTorch stores
+    it (nothing is packed), plain fp32 arithmetic under every policy.  One launch writes the partial sums of the weight AND the bias
+    gradient; tpgsr_reduce_partials finishes them on the side stream (_row_partials_grad: into the sinks in a recorded plan)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        _chk(x, w, b)
+        x, w = _c(x), _c(w)
+        N, H, W, Cin = x.shape
+        Cout = w.shape[0]
+        y = _new(x, N, H, W, Cout)
+        K.conv5x5_narrow_fwd(x, w, b, N, H, W, Cin, Cout, y)
+        ctx.save_for_backward(x, w, b)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, b = ctx.saved_tensors
+        N, H, W, Cin = x.shape
+        Cout = w.shape[0]
+        dy = _c(dy)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            K.conv5x5_narrow_bwd_data(dy, w, N, H, W, Cin, Cout, dx)
+        if ctx.needs_input_grad[1] or (b is not None and ctx.needs_input_grad[2]):
+            nblk, E = K.narrow5_wgrad_blocks(N, H, W), K.narrow5_row(Cin, Cout)
+            part = _new(x, nblk, E)
+            dw, *db = _row_partials_grad((w,) if b is None else (w, b), part, nblk, E,
+                                         lambda: K.conv5x5_narrow_bwd_weight(x, dy, N, H, W, Cin, Cout, part, nblk))
+            db = db[0] if db else None
+        return dx, dw, db
+
+
+def conv2d_narrow5x5(x, w, b=None, form: Optional[str] = None):
+    """nn.Conv2d(Cin, Cout <= 4, 5, padding=2) on an NHWC map, b: the bias [Cout] or None.  form "narrow": the direct kernels (Cin a
+    multiple of 4 up to 64); "matrix": conv2d(x, w, b, 2), the matrix-core route with Cout padded to a tile; None: NARROW5_DEFAULT_FORM.
+    Every refusal comes before a launch."""
+    if w.dim() != 4 or tuple(w.shape[2:]) != (5, 5) or not 1 <= w.shape[0] <= K.NARROW5_MAX_COUT:
+        raise ValueError(f"conv2d_narrow5x5: a [Cout <= {K.NARROW5_MAX_COUT}][Cin][5][5] weight, got {tuple(w.shape)}")
+    Cout, Cin = w.shape[:2]
+    if x.dim() != 4 or x.shape[-1] != Cin:
+        raise ValueError(f"conv2d_narrow5x5: input {tuple(x.shape)} is not (N, H, W, {Cin})")
+    if b is not None and tuple(b.shape) != (Cout,):
+        raise ValueError(f"conv2d_narrow5x5: bias {tuple(b.shape)} is not ({Cout},)")
+    unfit = {"narrow": f"the direct kernels take an input channel count that is a multiple of 4 up to {K.NARROW5_MAX_CIN}, "
+                       f"got {Cin} (use form='matrix')"} if (Cin % 4 or not 4 <= Cin <= K.NARROW5_MAX_CIN) else {}
+    if _choose_form("conv2d_narrow5x5", form, NARROW_FORMS, NARROW5_DEFAULT_FORM, unfit) == "matrix":
+        return conv2d(x, w, b, 2)
+    return _Conv2dNarrow5.apply(x, w, b)
+
+
+# the form `form=None` runs: decided by tools/lab/srcnn_step_time.py (profiles/srcnn_step_time.md)
+NARROW5_DEFAULT_FORM = "narrow"
 
 
 # ---- pooling / resampling -------------------------------------------------------------------------------------------------

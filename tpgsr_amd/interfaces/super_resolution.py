@@ -248,6 +248,7 @@ class TSRNTrainStep(_TrainStep):
         SRTrainStep(lapsrn.LapSRN(scale_factor=4), image_crit="l1_charbonnier", channels=3)      # --arch lapsrn, no --mask
         SRTrainStep(esrgan.RRDBNet(scale_factor=4), image_crit="l1", channels=3)                 # --arch esrgan, no --mask
         SRTrainStep(edsr.EDSR(scale_factor=4), image_crit="l1", channels=3)                      # --arch edsr, no --mask
+        SRTrainStep(srcnn.SRCNN(scale_factor=2), image_crit="mse", channels=3)                   # train_SRCNN.sh
     image_crit: the criterion interfaces/base.py:332-347 pairs with the architecture (`ImageCriterion` above).  channels: the reference's
     channel_num -- the step feeds lr[:, :channels] and compares with hr[:, :channels] (:410-416); the prefix is gathered by a kernel
     launch (tpgsr_copy_strided), so capture() / replay() work on it."""

@@ -1533,6 +1533,54 @@ def conv3x3_narrow_bwd_weight(x, dy, N, H, W, Cin, Cout, partial, nblk):
     _launch("tpgsr_conv3x3_narrow_bwd_weight", _p(x), _p(dy), N, H, W, Cin, Cout, _p(partial), nblk)
 
 
+# ---- direct 5x5 convolution to <= 4 output channels, optional bias (csrc/conv_narrow5.hip) ----------------------------
+NARROW5_MAX_COUT, NARROW5_MAX_CIN = 4, 64
+NARROW5_WGRAD_BLOCKS = 1024     # rows of the weight gradient's partial sums at most (one workgroup each)
+NARROW5_WGRAD_PIXELS = 64       # pixels a workgroup sums at least: small maps get fewer rows
+
+
+def narrow5_wgrad_blocks(N, H, W) -> int:
+    return max(1, min(NARROW5_WGRAD_BLOCKS, (N * H * W + NARROW5_WGRAD_PIXELS - 1) // NARROW5_WGRAD_PIXELS))
+
+
+def narrow5_row(Cin, Cout) -> int:
+    """floats of one row of the weight gradient's partial sums: the weight elements in w's order, then the bias gradient"""
+    return Cout * Cin * 25 + Cout
+
+
+def _narrow5_check(who, N, H, W, Cin, Cout, x, y, w=None, b=None):
+    """the refusals of the C launch functions, made before anything is launched (or recorded)"""
+    if not 1 <= Cout <= NARROW5_MAX_COUT:
+        raise ValueError(f"{who}: the direct kernels take 1 to {NARROW5_MAX_COUT} output channels, got {Cout}")
+    if Cin % 4 or not 4 <= Cin <= NARROW5_MAX_CIN:
+        raise ValueError(f"{who}: the direct kernels take an input channel count that is a multiple of 4 up to {NARROW5_MAX_CIN}, got {Cin}")
+    if min(N, H, W) < 1 or N * H * W >= 1 << 27:
+        raise ValueError(f"{who}: needs 1 <= N H W < 2^27 pixels, got {N} x {H} x {W}")
+    if x.numel() != N * H * W * Cin or y.numel() != N * H * W * Cout or (w is not None and w.numel() != Cout * Cin * 25) \
+            or (b is not None and b.numel() != Cout):
+        raise ValueError(f"{who}: tensor sizes do not match N {N}, H {H}, W {W}, Cin {Cin}, Cout {Cout}")
+
+
+def conv5x5_narrow_fwd(x, w, b, N, H, W, Cin, Cout, y):
+    """b: the bias [Cout] or None"""
+    _narrow5_check("conv5x5_narrow_fwd", N, H, W, Cin, Cout, x, y, w, b)
+    _launch("tpgsr_conv5x5_narrow_fwd", _p(x), _p(w), None if b is None else _p(b), N, H, W, Cin, Cout, _p(y))
+
+
+def conv5x5_narrow_bwd_data(dy, w, N, H, W, Cin, Cout, dx):
+    _narrow5_check("conv5x5_narrow_bwd_data", N, H, W, Cin, Cout, dx, dy, w)
+    _launch("tpgsr_conv5x5_narrow_bwd_data", _p(dy), _p(w), N, H, W, Cin, Cout, _p(dx))
+
+
+def conv5x5_narrow_bwd_weight(x, dy, N, H, W, Cin, Cout, partial, nblk):
+    """partial [nblk][narrow5_row(Cin, Cout)]: reduce_partials(partial, nblk, narrow5_row(Cin, Cout), dw | db, accumulate) finishes it"""
+    _narrow5_check("conv5x5_narrow_bwd_weight", N, H, W, Cin, Cout, x, dy)
+    if not 1 <= nblk <= 65536 or partial.numel() < nblk * narrow5_row(Cin, Cout):
+        raise ValueError(f"conv5x5_narrow_bwd_weight: partial holds {partial.numel()} floats, {nblk} workgroups write "
+                         f"{nblk * narrow5_row(Cin, Cout)}")
+    _launch("tpgsr_conv5x5_narrow_bwd_weight", _p(x), _p(dy), N, H, W, Cin, Cout, _p(partial), nblk)
+
+
 def hreduce(inp, N, H, W, C_, scale, out):
     _launch("tpgsr_hreduce", _p(inp), N, H, W, C_, scale, _p(out))
 

@@ -1,28 +1,70 @@
-"""SRCNN (reference: model/srcnn.py:109-145) -- BASELINE config C1 only: a CPU plumbing case (SURVEY.md section 8a
-row S1: "CPU, no kernel").  It is the one network of this package that is plain PyTorch, on purpose: C1 exists to
-check the harness / fixtures / timer without a GPU, it is not part of the MI355X hot path."""
+"""`--arch srcnn` and `--arch srcnn_tl` (reference: model/srcnn.py:109-145 SRCNN, :50-106 SRCNN_TL).
+
+SRCNN -- nearest-neighbour up-sampling, Conv2d(3, 64, 9) - ReLU - Conv2d(64, 32, 1) - ReLU - Conv2d(32, 3, 5), trained by train_SRCNN.sh
+through the `else:` branch of the loop (interfaces/super_resolution.py:409-424) on three channels with nn.MSELoss -- runs on the MI355X
+operator by operator on the HIP kernels (tpgsr_amd/functional.py), NHWC inside; its last layer, three output channels on the HR grid,
+runs on the direct narrow-output kernels (functional.conv2d_narrow5x5, csrc/conv_narrow5.hip).
+
+A CPU input takes the ONE deliberate stock-PyTorch path of this package: BASELINE config C1 is a plumbing
+case that checks the harness / fixtures / timer without a GPU, so `SRCNN()(cpu_tensor)` computes the same network with ATen on the same
+parameter tensors.  It is no fall-back: a device input never reaches it, and a missing kernel is an error there."""
 import torch
 from torch import nn
 
-from .nn_params import EngineHolder
+from .nn_params import Conv2dParams, EngineHolder
 
 
-class SRCNN(nn.Module):
+class SRCNN(EngineHolder, nn.Module):
+    """Same constructor signature, attribute names, state_dict keys and initial values (Conv2dParams draws what nn.Conv2d draws) as the
+    reference's.  scale_factor 2 and 4 are built and tested; the device path takes any integer factor and refuses another at its first
+    forward (the CPU path takes what F.interpolate takes).  `set_tail_form` names conv3's form (a measurement switch:
+    tools/lab/srcnn_step_time.py); None leaves functional.conv2d_narrow5x5's default."""
+
     def __init__(self, scale_factor=2, in_planes=3, STN=False, height=32, width=128):
         super().__init__()
         if STN:
             raise NotImplementedError("SRCNN+STN is not on the TPGSR path (train_SRCNN.sh runs without --STN)")
         self.upscale_factor = scale_factor
-        self.conv1 = nn.Conv2d(in_planes, 64, kernel_size=9, padding=4)
-        self.relu1 = nn.ReLU()
-        self.conv2 = nn.Conv2d(64, 32, kernel_size=1, padding=0)
-        self.relu2 = nn.ReLU()
-        self.conv3 = nn.Conv2d(32, in_planes, kernel_size=5, padding=2)
+        self.conv1 = Conv2dParams(in_planes, 64, 9, padding=4)
+        self.relu1 = nn.Identity()
+        self.conv2 = Conv2dParams(64, 32, 1, padding=0)
+        self.relu2 = nn.Identity()
+        self.conv3 = Conv2dParams(32, in_planes, 5, padding=2)
         self.stn = STN
+        self.tail_form = None
+
+    def set_tail_form(self, form):
+        from .. import functional as Fh
+        if form is not None and form not in Fh.NARROW_FORMS:
+            raise ValueError(f"SRCNN: tail form={form!r}, expected one of {Fh.NARROW_FORMS} or None")
+        self.tail_form = form
+
+    def _engine(self):
+        """engine adapter (tpgsr_amd/engine_functional.py PlainSREngine), as LapSRN's: the engine carries THIS module's factor"""
+        from .tl_common import sr_engine
+        eng = sr_engine(self, prior=False)
+        eng.scale = self.upscale_factor
+        return eng
+
+    def _forward_aten(self, x):
+        F = torch.nn.functional
+        x = F.interpolate(x, scale_factor=self.upscale_factor)
+        x = F.relu(F.conv2d(x, self.conv1.weight, self.conv1.bias, padding=4))
+        x = F.relu(F.conv2d(x, self.conv2.weight, self.conv2.bias))
+        return F.conv2d(x, self.conv3.weight, self.conv3.bias, padding=2)
 
     def forward(self, x):
-        x = torch.nn.functional.interpolate(x, scale_factor=self.upscale_factor)
-        return self.conv3(self.relu2(self.conv2(self.relu1(self.conv1(x)))))
+        from .. import functional as Fh
+        from .. import kernels as K
+        if not (x.is_cuda or K.DRYRUN):
+            return self._forward_aten(x)
+        s = self.upscale_factor
+        if isinstance(s, bool) or int(s) != s or s < 1:
+            raise ValueError(f"SRCNN: scale_factor={s!r}: the device path up-samples by an integer factor (tpgsr_resize_nearest_fwd)")
+        out = Fh.upsample_nearest(Fh.to_nhwc(x), int(s))
+        out = Fh.relu(self.conv1(out))
+        out = Fh.relu(self.conv2(out))
+        return Fh.to_nchw(Fh.conv2d_narrow5x5(out, self.conv3.weight, self.conv3.bias, form=self.tail_form))
 
 
 class SRCNN_TL(EngineHolder, nn.Module):
